@@ -4,6 +4,10 @@
 batch 128; N>1 = configs[3], weak scaling, RCCL all-reduce over xGMI).
 
 Contract: python bench.py --gpus N --steps K --warmup W
+A plain run sets up, warms up, times the K steps and prints the result
+line.  --dump-outputs DIR additionally writes what the last timed step
+computed (loss, loss-layer inputs, updated weights) as DIR/<name>.npy;
+--full adds the roofline and CPU-baseline legs to the result line.
 (N>1 ranks launched by torch.distributed.run; gloo is used only for
 rendezvous/ncclUniqueId exchange and the timing barrier — the engine's own
 RCCL communicator does the gradient collectives.)
@@ -195,6 +199,121 @@ def oracle_resnet50_step(batch):
     return time.time() - t0
 
 
+def roofline_from_perf(perf, model, dtype):
+    """roofline entry of the result line from the engine's per-kernel-class
+    event timings (ca.perf_snapshot() after the instrumented steps)."""
+    g = {"flops": 0.0, "ns": 0.0, "launches": 0}
+    for k, v in perf.items():
+        if k.startswith("gemm"):
+            g["flops"] += v["flops"]
+            g["ns"] += v["ns"]
+            g["launches"] += v["launches"]
+    achieved = g["flops"] / max(g["ns"], 1) * 1e9  # FLOP/s
+    # measured HBM bytes per GEMM-class launch, from the committed PMC
+    # capture (tools/pmc_traffic.py, FETCH_SIZE x2-corrected +
+    # WRITE_SIZE); null if not captured
+    traffic = None
+    pmc_path = os.path.join(REPO, "profiles",
+                            f"pmc_traffic_{model}.json")
+    if os.path.exists(pmc_path):
+        try:
+            pmc = json.load(open(pmc_path))
+            gc = pmc["classes"].get("gemm")
+            if gc and gc.get("launches"):
+                traffic = ((gc["fetch_bytes"] + gc["write_bytes"])
+                           / gc["launches"])
+        except Exception:
+            traffic = None
+    peak = PEAK_BF16_MFMA if dtype == "bf16" else PEAK_F32_MFMA
+    roofline = {
+        "bound": "mfma",
+        "achieved": achieved,
+        "peak": peak,
+        "unit": "TFLOP/s",
+        "frac": achieved / peak,
+        "traffic": traffic,
+        "traffic_note": ("HBM bytes/launch of the GEMM class, "
+                        "profiles/pmc_traffic_*.json "
+                        "(FETCH_SIZE x2 + WRITE_SIZE)")
+                       if traffic is not None else None,
+        "kernel": "gemm_f32 (conv/IP contractions)",
+        "kernel_time_frac": None,
+    }
+    tot_ns = sum(v["ns"] for v in perf.values())
+    if tot_ns > 0:
+        roofline["kernel_time_frac"] = g["ns"] / tot_ns
+    roofline["classes"] = {
+        k: {"ms": v["ns"] / 1e6,
+            "tf": v["flops"] / max(v["ns"], 1) / 1e3}
+        for k, v in sorted(perf.items(), key=lambda kv: -kv[1]["ns"])}
+    return roofline
+
+
+DUMP_BUDGET = 48 << 20  # bytes of float32 over all dumped arrays (< 64 MB)
+
+
+def loss_bottoms(model):
+    """Blob names feeding the TRAIN-phase loss layers, from the model spec."""
+    spec = json.load(open(os.path.join(REPO, "models", "specs",
+                                       f"{model}.json")))
+    names = []
+    for k, v in spec:
+        if k != "layer" or dict(v).get("type") != "SoftmaxWithLoss":
+            continue
+        inc = dict(v).get("include")
+        if inc and dict(inc).get("phase") == "TEST":
+            continue
+        names.append([b for kk, b in v if kk == "bottom"][0])
+    return names
+
+
+def sample_positions(key, count, cap):
+    """Sorted positions kept of array number `key` (`count` elements) when
+    only `cap` fit: a function of key, count and cap alone, so every run
+    and every build keeps the same elements.  None = the array whole."""
+    import numpy as np
+    if count <= cap:
+        return None
+    return np.sort(np.random.default_rng(1371 + key).choice(
+        count, cap, replace=False))
+
+
+def dump_outputs(solver, model, out_dir):
+    """What a caller of solver.step() is left with after the last timed
+    step, as out_dir/<name>.npy (float32): the loss of that step's forward
+    pass, the loss layers' inputs (logits of the last batch) and every
+    learnable blob after the update.  Arrays are written whole while
+    DUMP_BUDGET allows; otherwise each array larger than a common cap
+    keeps sample_positions() of its flattened elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    net = solver.net
+    # (file stem, sampling key, element count, getter)
+    arrays = []
+    for j, name in enumerate(loss_bottoms(model)):
+        arrays.append(("blob_" + name.replace("/", "_"), 100000 + j,
+                       int(np.prod(net.blob_shape(name))),
+                       lambda name=name: net.blob(name)))
+    for i in range(net.num_params()):
+        lname, bi, cnt = net.param_info(i)
+        arrays.append((f"param_{i:03d}_{lname.replace('/', '_')}_{bi}", i,
+                       cnt, lambda i=i: net.param(i)))
+    cap = max(cnt for _, _, cnt, _ in arrays)
+    while 4 + 4 * sum(min(cnt, cap) for _, _, cnt, _ in arrays) > DUMP_BUDGET:
+        if cap == 1:
+            raise RuntimeError("dump budget too small for one element per "
+                               f"array ({len(arrays)} arrays)")
+        cap //= 2
+    np.save(os.path.join(out_dir, "loss.npy"),
+            np.array([solver.loss()], np.float32))
+    for stem, key, cnt, get in arrays:
+        a = get()
+        idx = sample_positions(key, cnt, cap)
+        if idx is not None:
+            a = a.ravel()[idx]
+        np.save(os.path.join(out_dir, stem + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -206,6 +325,10 @@ def main():
     # bf16 = mixed precision (bf16 MFMA, fp32 accumulation/storage) — a
     # SECOND reported line; the BASELINE contract metric stays f32
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
+    # everything beyond the headline figure (per-kernel roofline leg, CPU
+    # baseline) runs only with --full
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -283,66 +406,30 @@ def main():
 
     value = world * args.batch * args.steps / elapsed
 
-    # roofline leg: 3 instrumented steps, HIP-event timed per kernel class
-    # on the launching stream.  ALL ranks step (the collectives are inside
-    # the step — a rank-0-only step would deadlock the communicator).
-    ca.perf_reset()
-    ca.set_perf_timing(True)
-    solver.step(1 if cpu_dry else 3)
-    ca.device_synchronize()
-    ca.set_perf_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(solver, args.model, args.dump_outputs)
+
+    if args.full:
+        # roofline leg: 3 instrumented steps, HIP-event timed per kernel
+        # class on the launching stream.  ALL ranks step (the collectives
+        # are inside the step — a rank-0-only step would deadlock the
+        # communicator).
+        ca.perf_reset()
+        ca.set_perf_timing(True)
+        solver.step(1 if cpu_dry else 3)
+        ca.device_synchronize()
+        ca.set_perf_timing(False)
     result = None
     if rank == 0:
-        perf = ca.perf_snapshot()
-        g = {"flops": 0.0, "ns": 0.0, "launches": 0}
-        for k, v in perf.items():
-            if k.startswith("gemm"):
-                g["flops"] += v["flops"]
-                g["ns"] += v["ns"]
-                g["launches"] += v["launches"]
-        achieved = g["flops"] / max(g["ns"], 1) * 1e9  # FLOP/s
-        # measured HBM bytes per GEMM-class launch, from the committed PMC
-        # capture (tools/pmc_traffic.py, FETCH_SIZE x2-corrected +
-        # WRITE_SIZE per MI355X_MICROARCH.md §HBM); null if not captured
-        traffic = None
-        pmc_path = os.path.join(REPO, "profiles",
-                                f"pmc_traffic_{args.model}.json")
-        if os.path.exists(pmc_path):
-            try:
-                pmc = json.load(open(pmc_path))
-                gc = pmc["classes"].get("gemm")
-                if gc and gc.get("launches"):
-                    traffic = ((gc["fetch_bytes"] + gc["write_bytes"])
-                               / gc["launches"])
-            except Exception:
-                traffic = None
-        peak = PEAK_BF16_MFMA if args.dtype == "bf16" else PEAK_F32_MFMA
-        roofline = {
-            "bound": "mfma",
-            "achieved": achieved,
-            "peak": peak,
-            "unit": "TFLOP/s",
-            "frac": achieved / peak,
-            "traffic": traffic,
-            "traffic_note": ("HBM bytes/launch of the GEMM class, "
-                            "profiles/pmc_traffic_*.json "
-                            "(FETCH_SIZE x2 + WRITE_SIZE)")
-                           if traffic is not None else None,
-            "kernel": "gemm_f32 (conv/IP contractions)",
-            "kernel_time_frac": None,
-        }
-        tot_ns = sum(v["ns"] for v in perf.values())
-        if tot_ns > 0:
-            roofline["kernel_time_frac"] = g["ns"] / tot_ns
-        roofline["classes"] = {
-            k: {"ms": v["ns"] / 1e6,
-                "tf": v["flops"] / max(v["ns"], 1) / 1e3}
-            for k, v in sorted(perf.items(), key=lambda kv: -kv[1]["ns"])}
+        roofline = None
+        if args.full:
+            roofline = roofline_from_perf(ca.perf_snapshot(), args.model,
+                                          args.dtype)
 
         cpu_baseline = None
         # the committed oracle walker restates ResNet-50 only; pairing it
         # with another model's metric would be wrong — omit instead
-        if world == 1 and not args.no_cpu_baseline and \
+        if args.full and world == 1 and not args.no_cpu_baseline and \
                 args.model == "resnet50" and not cpu_dry:
             bcpu = 4
             t_cpu = oracle_resnet50_step(bcpu)

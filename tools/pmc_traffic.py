@@ -70,7 +70,7 @@ def run_pass(counter, model, steps, tag):
            "--output-format", "csv", "--",
            sys.executable, os.path.join(REPO, "bench.py"),
            "--model", model, "--steps", str(steps), "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     env = dict(os.environ, TMPDIR="/tmp")
     r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True,
                        text=True)
