@@ -65,6 +65,7 @@ _lib.caffe_net_create.restype = ctypes.c_void_p
 _lib.caffe_net_loss.restype = ctypes.c_float
 _lib.caffe_set_random_seed.argtypes = [ctypes.c_uint64]
 _lib.caffe_set_compute.argtypes = [ctypes.c_char_p]
+_lib.caffe_gemm_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
 
 _f32p = ctypes.POINTER(ctypes.c_float)
 _lib.caffe_net_blob_get.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int,
@@ -159,6 +160,32 @@ def perf_snapshot():
 
 def perf_reset():
     _ck(_lib.caffe_perf_reset())
+
+
+def gemm_trace(enable):
+    """Record which GEMM kernel every conv/IP contraction is dispatched to
+    (off by default; enabling clears the log, which holds 4096 records)."""
+    _ck(_lib.caffe_gemm_trace(1 if enable else 0))
+
+
+def gemm_trace_read():
+    """The recorded routes, one dict per gemm call: fam (slim32 | slim64 |
+    f32_128 | bf16_128 | bf16_wide), ta, tb, sk (1 = no split-K), kw (the
+    128-tile kernels' intra-block K split), M, N, K, tm, tn (tile rows /
+    columns), av, bv (none | chan | im2col) with sh, sw, epi (none | plain |
+    scatter | sscatter), bias (none | row | col), relu."""
+    n = _lib.caffe_gemm_trace_read(None, 0)
+    if n < 0:
+        raise CaffeError(_lib.caffe_last_error().decode())
+    buf = ctypes.create_string_buffer(n + 1)
+    if _lib.caffe_gemm_trace_read(buf, n + 1) < 0:
+        raise CaffeError(_lib.caffe_last_error().decode())
+    out = []
+    for line in buf.value.decode().splitlines():
+        rec = dict(kv.split("=", 1) for kv in line.split())
+        out.append({k: int(v) if v.lstrip("-").isdigit() else v
+                    for k, v in rec.items()})
+    return out
 
 
 class Net:

@@ -470,6 +470,19 @@ int caffe_perf_snapshot(char* names, int name_cap, long* launches,
   API_CATCH
 }
 
+int caffe_gemm_trace(int enable) {
+  API_TRY
+  gpu::gemm_trace(enable != 0);
+  return 0;
+  API_CATCH
+}
+
+int caffe_gemm_trace_read(char* buf, int cap) {
+  API_TRY
+  return (int)gpu::gemm_trace_read(buf, cap);
+  API_CATCH
+}
+
 int caffe_perf_reset(void) {
   for (auto& kv : Engine::get().perf()) {
     kv.second.launches = 0;

@@ -16,6 +16,12 @@
 // ReLU, NCHW scatter.  Deterministic split-K (partial slabs + fixed-order
 // reduce, no atomics — SURVEY.md §7 hard part (b)) for the few-tile/huge-K
 // wgrad shapes.
+#include <atomic>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
 #include "gemm_common.hpp"
 
 namespace camd {
@@ -867,6 +873,88 @@ static void launch_slim(bool transA, bool transB, dim3 grid, dim3 block,
                        0, s, g);
 }
 
+// ---- route trace: which kernel gemm() picked for a call, and with which
+// views / epilogue.  Host-side only; off by default (one relaxed load per
+// call), capped so a forgotten enable cannot grow without bound.
+enum RouteFam { kSlim32, kSlim64, kF32_128, kBf16_128, kBf16Wide };
+struct GemmRoute {
+  long M, N, K, tm, tn;
+  int sk, sh, sw;
+  unsigned char fam, ta, tb, kw, av, bv, epi, bias, relu;
+};
+constexpr size_t kTraceCap = 4096;
+static std::atomic<bool> g_trace_on{false};
+static std::mutex g_trace_mu;
+static std::vector<GemmRoute> g_trace_log;
+
+static int view_kind(const GemmView* v) {  // 0 none, 1 chan, 2 im2col
+  return !v || !v->spad ? 0 : (v->kh > 0 ? 2 : 1);
+}
+
+static void trace_route(int fam, bool ta, bool tb, int sk, long M, long N,
+                        long K, long tm, long tn, const GemmEpi* epi,
+                        const GemmView* av, const GemmView* bv) {
+  GemmRoute r{};
+  r.M = M;
+  r.N = N;
+  r.K = K;
+  r.tm = tm;
+  r.tn = tn;
+  r.sk = sk;
+  r.fam = (unsigned char)fam;
+  r.ta = ta;
+  r.tb = tb;
+  // intra-block K split of the 128-tile kernels (mirrors k_gemm_f32 /
+  // k_gemm_bf16: waves not needed for M or N <= 64 take K-ranges)
+  r.kw = (fam == kF32_128 || fam == kBf16_128)
+             ? 4 / ((M > 64 ? 2 : 1) * (N > 64 ? 2 : 1))
+             : 1;
+  r.av = (unsigned char)view_kind(av);
+  r.bv = (unsigned char)view_kind(bv);
+  const GemmView* iv = r.bv == 2 ? bv : (r.av == 2 ? av : nullptr);
+  r.sh = iv ? iv->sh : 1;
+  r.sw = iv ? iv->sw : 1;
+  // 0 none, 1 plain, 2 NCHW scatter, 3 strided scatter
+  r.epi = !epi ? 0 : (epi->spad <= 0 ? 1 : (epi->OWo > 0 ? 3 : 2));
+  r.bias = !epi || !epi->bias ? 0 : (epi->bias_per_col ? 2 : 1);
+  r.relu = epi && epi->relu;
+  std::lock_guard<std::mutex> lk(g_trace_mu);
+  if (g_trace_log.size() < kTraceCap) g_trace_log.push_back(r);
+}
+
+void gemm_trace(bool enable) {
+  std::lock_guard<std::mutex> lk(g_trace_mu);
+  if (enable) {
+    g_trace_log.clear();
+    g_trace_log.reserve(kTraceCap);
+  }
+  g_trace_on.store(enable, std::memory_order_relaxed);
+}
+
+long gemm_trace_read(char* buf, long cap) {
+  static const char* const fam[] = {"slim32", "slim64", "f32_128",
+                                    "bf16_128", "bf16_wide"};
+  static const char* const view[] = {"none", "chan", "im2col"};
+  static const char* const epi[] = {"none", "plain", "scatter", "sscatter"};
+  static const char* const bias[] = {"none", "row", "col"};
+  std::lock_guard<std::mutex> lk(g_trace_mu);
+  long len = 0;
+  if (cap > 0) buf[0] = 0;
+  for (const GemmRoute& r : g_trace_log) {
+    char line[256];
+    const int n = snprintf(
+        line, sizeof(line),
+        "fam=%s ta=%d tb=%d sk=%d kw=%d M=%ld N=%ld K=%ld tm=%ld tn=%ld "
+        "av=%s bv=%s sh=%d sw=%d epi=%s bias=%s relu=%d\n",
+        fam[r.fam], r.ta, r.tb, r.sk, r.kw, r.M, r.N, r.K, r.tm, r.tn,
+        view[r.av], view[r.bv], r.sh, r.sw, epi[r.epi], bias[r.bias],
+        r.relu);
+    if (len + n < cap) memcpy(buf + len, line, (size_t)n + 1);
+    len += n;
+  }
+  return len;
+}
+
 void gemm(hipStream_t s, bool transA, bool transB, long M, long N, long K,
           float alpha, const float* A, long lda, const float* B, long ldb,
           float beta, float* C, long ldc, const GemmEpi* epi,
@@ -951,6 +1039,17 @@ void gemm(hipStream_t s, bool transA, bool transB, long M, long N, long K,
   if (!epi && beta == 0.f && g.tiles < sk_target && K > 4 * BK) {
     SK = (int)std::min<long>(
         {sk_target / g.tiles + 1, (K + 4 * BK - 1) / (4 * BK), 256});
+  }
+  if (g_trace_on.load(std::memory_order_relaxed)) {
+    // (the CAFFE_GEMM_V2 experiment shares the 128-tile grid and is
+    // reported as f32_128)
+    const int fam = TMv == 32    ? kSlim32
+                    : TMv == 64  ? kSlim64
+                    : TMv == 256 ? kBf16Wide
+                    : Engine::get().gemm_bf16 ? kBf16_128
+                                              : kF32_128;
+    trace_route(fam, transA, transB, SK, M, N, K, tm, tn, epi, aview,
+                bview);
   }
   const char* pcls = !transA ? (!transB ? "gemm_nn" : "gemm_nt")
                             : (!transB ? "gemm_tn" : "gemm_tt");

@@ -87,6 +87,14 @@ void gemm(hipStream_t s, bool transA, bool transB, long M, long N, long K,
           float beta, float* C, long ldc, const GemmEpi* epi = nullptr,
           const GemmView* aview = nullptr, const GemmView* bview = nullptr);
 
+// Route trace of gemm()'s dispatch (off by default; for the tests that pin
+// which kernel a shape reaches).  Enabling clears the log; disabling keeps
+// it readable.  gemm_trace_read() writes one "key=value ..." line per
+// traced call into buf (at most cap bytes, always \0-terminated when
+// cap > 0) and returns the length of the full text.
+void gemm_trace(bool enable);
+long gemm_trace_read(char* buf, long cap);
+
 // db[c] = Σ_n Σ_s dy[n][c][s] (deterministic)
 void bias_grad(hipStream_t s, const float* dy, int N, int C, long S,
                float* db);

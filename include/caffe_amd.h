@@ -150,6 +150,15 @@ int caffe_device_synchronize(void);
 int caffe_perf_snapshot(char* names, int name_cap, long* launches,
                         double* flops, double* bytes, double* ns, int max_rows);
 int caffe_perf_reset(void);
+/* GEMM route trace (off by default): while enabled, every conv/IP
+ * contraction records which kernel the dispatch picked (family, transposes,
+ * split-K, tile grid, operand views, epilogue).  Enabling clears the log;
+ * it holds at most 4096 records.  _read writes one "key=value ..." line per
+ * record into buf (\0-terminated, truncated at a line boundary to cap) and
+ * returns the length of the full text, so a caller can size the buffer with
+ * a first call of cap 0. */
+int caffe_gemm_trace(int enable);
+int caffe_gemm_trace_read(char* buf, int cap);
 
 #ifdef __cplusplus
 }

@@ -14,11 +14,25 @@ from oracle import oracle as orc
 rng = np.random.default_rng(20250915)
 
 
+def round_bf16(a):
+    """float32 -> nearest bfloat16 (ties to even) -> float32, in numpy (the
+    engine's tests never import torch, see conftest.py)."""
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32)
+    u = (u + (((u >> 16) & 1) + 0x7FFF)) & np.uint32(0xFFFF0000)
+    return u.view(np.float32)
+
+
 def check_conv(mode, N=2, C=8, H=13, W=13, Co=16, k=3, s=1, p=1, grp=1,
-               bias=True, d=1):
-    x = rng.standard_normal((N, C, H, W)).astype(np.float32)
-    w = (rng.standard_normal((Co, C // grp, k, k)) * 0.2).astype(np.float32)
-    b = rng.standard_normal(Co).astype(np.float32) if bias else None
+               bias=True, d=1, quant=None, errs=None):
+    """quant: applied to x, w, b and dy before both the engine and the
+    oracle see them (e.g. round_bf16).  errs: a dict that receives the
+    measured relerr of y / dx / dw / db before each is asserted."""
+    quant = quant or (lambda a: a)
+    errs = {} if errs is None else errs
+    x = quant(rng.standard_normal((N, C, H, W)).astype(np.float32))
+    w = quant(
+        (rng.standard_normal((Co, C // grp, k, k)) * 0.2).astype(np.float32))
+    b = quant(rng.standard_normal(Co).astype(np.float32)) if bias else None
     body = f"""layer {{
   name: "conv"
   type: "Convolution"
@@ -36,21 +50,66 @@ def check_conv(mode, N=2, C=8, H=13, W=13, Co=16, k=3, s=1, p=1, grp=1,
 }}"""
     y_ref = orc.conv_fwd(x, w, b, pad=(p, p), stride=(s, s), dil=(d, d),
                          group=grp)
-    dy = rng.standard_normal(y_ref.shape).astype(np.float32)
+    dy = quant(rng.standard_normal(y_ref.shape).astype(np.float32))
     net, y = run_layer(mode, [(N, C, H, W)], body, [x],
                        params=[w, b] if bias else [w], top_diff=dy)
-    assert relerr(y, y_ref) < TOL, f"conv fwd {relerr(y, y_ref)}"
+    errs["y"] = relerr(y, y_ref)
+    assert errs["y"] < TOL, f"conv fwd {errs['y']}"
     dx_ref, dw_ref, db_ref = orc.conv_bwd(x, w, dy, pad=(p, p),
                                           stride=(s, s), dil=(d, d),
                                           group=grp, want_db=bias)
-    assert relerr(net.blob("in0", diff=True), dx_ref) < TOL, "conv dx"
-    assert relerr(net.param(0, diff=True),
-                  dw_ref.ravel()) < TOL, "conv dw"
+    errs["dx"] = relerr(net.blob("in0", diff=True), dx_ref)
+    assert errs["dx"] < TOL, f"conv dx {errs['dx']}"
+    errs["dw"] = relerr(net.param(0, diff=True), dw_ref.ravel())
+    assert errs["dw"] < TOL, f"conv dw {errs['dw']}"
     if bias:
-        assert relerr(net.param(1, diff=True), db_ref) < TOL, "conv db"
+        errs["db"] = relerr(net.param(1, diff=True), db_ref)
+        assert errs["db"] < TOL, f"conv db {errs['db']}"
 
 
-def check_ip(mode, M=4, K=32, Nout=10):
+def check_conv_relu(mode, N=2, C=8, H=13, W=13, Co=16, k=3, s=1, p=1,
+                    errs=None):
+    """Conv with bias followed by an in-place ReLU (in GPU mode the net
+    folds the ReLU into the GEMM epilogue): y against relu(oracle conv),
+    dx / dW against the oracle's conv backward of dy * (y > 0).  dy is
+    zeroed where the pre-activation lies within 1e-3 of 0, so a sign that
+    legitimately differs in the last fp32 bits cannot move a gradient."""
+    errs = {} if errs is None else errs
+    x = rng.standard_normal((N, C, H, W)).astype(np.float32)
+    w = (rng.standard_normal((Co, C, k, k)) * 0.2).astype(np.float32)
+    b = rng.standard_normal(Co).astype(np.float32)
+    body = f"""layer {{
+  name: "conv"
+  type: "Convolution"
+  bottom: "in0"
+  top: "out"
+  convolution_param {{
+    num_output: {Co} kernel_size: {k} stride: {s} pad: {p}
+  }}
+}}
+layer {{ name: "relu" type: "ReLU" bottom: "out" top: "out" }}"""
+    pre = orc.conv_fwd(x, w, b, pad=(p, p), stride=(s, s))
+    y_ref = np.maximum(pre, 0)
+    dy = rng.standard_normal(pre.shape).astype(np.float32)
+    dy[np.abs(pre) < 1e-3] = 0
+    net, y = run_layer(mode, [(N, C, H, W)], body, [x], params=[w, b],
+                       top_diff=dy)
+    errs["y"] = relerr(y, y_ref)
+    assert errs["y"] < TOL, f"conv+relu fwd {errs['y']}"
+    assert np.asarray(y).min() >= 0
+    dpre = (dy * (pre > 0)).astype(np.float32)
+    dx_ref, dw_ref, db_ref = orc.conv_bwd(x, w, dpre, pad=(p, p),
+                                          stride=(s, s), want_db=True)
+    errs["dx"] = relerr(net.blob("in0", diff=True), dx_ref)
+    assert errs["dx"] < TOL, f"conv+relu dx {errs['dx']}"
+    errs["dw"] = relerr(net.param(0, diff=True), dw_ref.ravel())
+    assert errs["dw"] < TOL, f"conv+relu dw {errs['dw']}"
+    errs["db"] = relerr(net.param(1, diff=True), db_ref)
+    assert errs["db"] < TOL, f"conv+relu db {errs['db']}"
+
+
+def check_ip(mode, M=4, K=32, Nout=10, errs=None):
+    errs = {} if errs is None else errs
     x = rng.standard_normal((M, K)).astype(np.float32)
     w = rng.standard_normal((Nout, K)).astype(np.float32) * 0.2
     w = w.astype(np.float32)
@@ -66,11 +125,15 @@ def check_ip(mode, M=4, K=32, Nout=10):
     dy = rng.standard_normal(y_ref.shape).astype(np.float32)
     net, y = run_layer(mode, [(M, K)], body, [x], params=[w, b],
                        top_diff=dy)
-    assert relerr(y, y_ref) < TOL
+    errs["y"] = relerr(y, y_ref)
+    assert errs["y"] < TOL, f"ip fwd {errs['y']}"
     dx_ref, dw_ref, db_ref = orc.ip_bwd(x, w, dy)
-    assert relerr(net.blob("in0", diff=True), dx_ref) < TOL
-    assert relerr(net.param(0, diff=True), dw_ref.ravel()) < TOL
-    assert relerr(net.param(1, diff=True), db_ref) < TOL
+    errs["dx"] = relerr(net.blob("in0", diff=True), dx_ref)
+    assert errs["dx"] < TOL, f"ip dx {errs['dx']}"
+    errs["dw"] = relerr(net.param(0, diff=True), dw_ref.ravel())
+    assert errs["dw"] < TOL, f"ip dw {errs['dw']}"
+    errs["db"] = relerr(net.param(1, diff=True), db_ref)
+    assert errs["db"] < TOL, f"ip db {errs['db']}"
 
 
 def check_pool(mode, pool="MAX", N=2, C=4, H=13, W=13, k=3, s=2, p=0):

@@ -60,6 +60,32 @@ def test_conv_bf16(cfg):
     assert _relerr(net.param(0, diff=True), dw_ref) < BTOL, "dW"
 
 
+@pytest.mark.parametrize("name", ["A", "B", "C", "E1", "E2", "E3", "F1",
+                                  "G1", "H2"])
+def test_conv_bf16_exact_inputs(name):
+    """bf16 kernels at the fp32 tolerance: x, w, b and dy are rounded to
+    bf16 first (layer_checks.round_bf16, the numpy equivalent of a round
+    trip through torch.bfloat16), so the kernel's own input rounding is the
+    identity; products of bf16 values are exact in fp32 and the MFMA
+    accumulates in fp32, so y, dx, dW and db must match the float64 oracle
+    on the same rounded arrays at TOL = 1e-4 (an fp32-accumulated
+    reference alone sits at 1.5e-7 at the largest shape).  The traced
+    routes must be exactly the bf16-mode routes of the case table in
+    test_gemm_routes.py: bf16_wide for M > 128 with N > 128, bf16_128 for
+    the other M > 64 routes, the fp32 slim kernels for M <= 64."""
+    from layer_checks import check_conv, round_bf16
+    from test_gemm_routes import (BF16_ROUTES, CONV_CASES, assert_routes,
+                                  traced)
+
+    errs = {}
+    try:
+        trace = traced(lambda: check_conv("gpu", quant=round_bf16,
+                                          errs=errs, **CONV_CASES[name][0]))
+    finally:
+        print("relerr", {k: f"{v:.2e}" for k, v in errs.items()})
+    assert_routes(trace, BF16_ROUTES[name])
+
+
 def test_conv_bf16_grouped():
     # AlexNet-style grouped conv under bf16 compute (group GEMM slices)
     N, C, H, W, Co, k, p, grp = 2, 8, 14, 14, 16, 5, 2, 2
