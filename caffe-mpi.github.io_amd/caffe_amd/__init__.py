@@ -66,6 +66,7 @@ _lib.caffe_net_loss.restype = ctypes.c_float
 _lib.caffe_set_random_seed.argtypes = [ctypes.c_uint64]
 _lib.caffe_set_compute.argtypes = [ctypes.c_char_p]
 _lib.caffe_gemm_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
+_lib.caffe_kernel_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
 
 _f32p = ctypes.POINTER(ctypes.c_float)
 _lib.caffe_net_blob_get.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int,
@@ -174,11 +175,15 @@ def gemm_trace_read():
     128-tile kernels' intra-block K split), M, N, K, tm, tn (tile rows /
     columns), av, bv (none | chan | im2col) with sh, sw, epi (none | plain |
     scatter | sscatter), bias (none | row | col), relu."""
-    n = _lib.caffe_gemm_trace_read(None, 0)
+    return _trace_records(_lib.caffe_gemm_trace_read)
+
+
+def _trace_records(read):
+    n = read(None, 0)
     if n < 0:
         raise CaffeError(_lib.caffe_last_error().decode())
     buf = ctypes.create_string_buffer(n + 1)
-    if _lib.caffe_gemm_trace_read(buf, n + 1) < 0:
+    if read(buf, n + 1) < 0:
         raise CaffeError(_lib.caffe_last_error().decode())
     out = []
     for line in buf.value.decode().splitlines():
@@ -186,6 +191,24 @@ def gemm_trace_read():
         out.append({k: int(v) if v.lstrip("-").isdigit() else v
                     for k, v in rec.items()})
     return out
+
+
+def kernel_trace(enable):
+    """Record which specialised kernel the pooling, BatchNorm-statistics,
+    LRN, softmax and segmented-SGD launch wrappers pick (off by default;
+    enabling clears the log, which holds 4096 records)."""
+    _ck(_lib.caffe_kernel_trace(1 if enable else 0))
+
+
+def kernel_trace_read():
+    """The recorded launches in call order, one dict per wrapper call:
+    op (pool_max_fwd | pool_max_bwd | pool_ave_fwd | pool_ave_bwd |
+    bn_fwd_stats | bn_bwd_stats | lrn_fwd | lrn_bwd | softmax_fwd | sgd_seg)
+    and, by op: var (k3 | k3s1 | k3s2 | generic for max pooling, v4 | scalar
+    for BN, ring5 | generic for LRN); nb and span_max (BN batch slices and
+    the largest per-block span); odd (LRN: N*H*W is odd); rows, C, blocks
+    (softmax); lo, hi, nseg (SGD bucket range in the param arena)."""
+    return _trace_records(_lib.caffe_kernel_trace_read)
 
 
 class Net:

@@ -483,6 +483,19 @@ int caffe_gemm_trace_read(char* buf, int cap) {
   API_CATCH
 }
 
+int caffe_kernel_trace(int enable) {
+  API_TRY
+  gpu::kernel_trace(enable != 0);
+  return 0;
+  API_CATCH
+}
+
+int caffe_kernel_trace_read(char* buf, int cap) {
+  API_TRY
+  return (int)gpu::kernel_trace_read(buf, cap);
+  API_CATCH
+}
+
 int caffe_perf_reset(void) {
   for (auto& kv : Engine::get().perf()) {
     kv.second.launches = 0;

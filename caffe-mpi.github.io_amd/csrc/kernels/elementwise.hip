@@ -11,6 +11,12 @@
 // conv_layer.cu:43-48).
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
 #include "../math.hpp"
 
 namespace camd {
@@ -21,6 +27,109 @@ static inline int nblocks(long n, int per_thread = 1) {
   long b = (n + (long)TPB * per_thread - 1) / ((long)TPB * per_thread);
   return (int)std::min<long>(b, 2048);
 }
+
+// ---- variant trace: which specialisation a launch wrapper below picked,
+// and the launch-shaping numbers a test cannot see from outside (BN slice
+// split, LRN odd tail, softmax grid, SGD bucket range).  Host-side only;
+// off by default (one relaxed load per wrapper call), capped like the GEMM
+// route trace.  Every field is passed from the branch / expression that
+// launches, so the log cannot disagree with what ran.
+enum KOp {
+  kPoolMaxFwd, kPoolMaxBwd, kPoolAveFwd, kPoolAveBwd, kBnFwdStats,
+  kBnBwdStats, kLrnFwd, kLrnBwd, kSoftmaxFwd, kSgdSeg
+};
+enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
+            kVarScalar, kVarRing5 };
+struct KernelRec {
+  long a, b, c;  // per-op fields, see kernel_trace_read
+  unsigned char op, var;
+};
+constexpr size_t kKTraceCap = 4096;
+static std::atomic<bool> g_ktrace_on{false};
+static std::mutex g_ktrace_mu;
+static std::vector<KernelRec> g_ktrace_log;
+
+static void ktrace_push(int op, int var, long a, long b, long c) {
+  std::lock_guard<std::mutex> lk(g_ktrace_mu);
+  if (g_ktrace_log.size() < kKTraceCap)
+    g_ktrace_log.push_back(
+        KernelRec{a, b, c, (unsigned char)op, (unsigned char)var});
+}
+static inline void ktrace(int op, int var = kVarNone, long a = 0, long b = 0,
+                          long c = 0) {
+  if (g_ktrace_on.load(std::memory_order_relaxed))
+    ktrace_push(op, var, a, b, c);
+}
+// BN stats: the largest per-block span (n1 - n0) * per over the nb batch
+// slices, with the slice bounds of k_bn_*_stats*; computed only when tracing
+static inline void ktrace_bn(int op, int var, int N, int nb, long per) {
+  if (!g_ktrace_on.load(std::memory_order_relaxed)) return;
+  long span_max = 0;
+  for (int slice = 0; slice < nb; ++slice) {
+    const int n0 = (int)((long)N * slice / nb);
+    const int n1 = (int)((long)N * (slice + 1) / nb);
+    span_max = std::max(span_max, (n1 - n0) * per);
+  }
+  ktrace_push(op, var, nb, span_max, 0);
+}
+
+void kernel_trace(bool enable) {
+  std::lock_guard<std::mutex> lk(g_ktrace_mu);
+  if (enable) {
+    g_ktrace_log.clear();
+    g_ktrace_log.reserve(kKTraceCap);
+  }
+  g_ktrace_on.store(enable, std::memory_order_relaxed);
+}
+
+long kernel_trace_read(char* buf, long cap) {
+  static const char* const op[] = {
+      "pool_max_fwd", "pool_max_bwd", "pool_ave_fwd", "pool_ave_bwd",
+      "bn_fwd_stats", "bn_bwd_stats", "lrn_fwd",      "lrn_bwd",
+      "softmax_fwd",  "sgd_seg"};
+  static const char* const var[] = {"",        "k3", "k3s1",   "k3s2",
+                                    "generic", "v4", "scalar", "ring5"};
+  std::lock_guard<std::mutex> lk(g_ktrace_mu);
+  long len = 0;
+  if (cap > 0) buf[0] = 0;
+  for (const KernelRec& r : g_ktrace_log) {
+    char line[160];
+    int n = 0;
+    switch (r.op) {
+      case kPoolMaxFwd:
+      case kPoolMaxBwd:
+        n = snprintf(line, sizeof(line), "op=%s var=%s\n", op[r.op],
+                     var[r.var]);
+        break;
+      case kPoolAveFwd:
+      case kPoolAveBwd:
+        n = snprintf(line, sizeof(line), "op=%s\n", op[r.op]);
+        break;
+      case kBnFwdStats:
+      case kBnBwdStats:
+        n = snprintf(line, sizeof(line), "op=%s var=%s nb=%ld span_max=%ld\n",
+                     op[r.op], var[r.var], r.a, r.b);
+        break;
+      case kLrnFwd:
+      case kLrnBwd:
+        n = snprintf(line, sizeof(line), "op=%s var=%s odd=%ld\n", op[r.op],
+                     var[r.var], r.a);
+        break;
+      case kSoftmaxFwd:
+        n = snprintf(line, sizeof(line), "op=%s rows=%ld C=%ld blocks=%ld\n",
+                     op[r.op], r.a, r.b, r.c);
+        break;
+      default:
+        n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld\n",
+                     op[r.op], r.a, r.b, r.c);
+        break;
+    }
+    if (len + n < cap) memcpy(buf + len, line, (size_t)n + 1);
+    len += n;
+  }
+  return len;
+}
+
 #define GRID_STRIDE(i, n)                                        \
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); \
        i += (long)gridDim.x * blockDim.x)
@@ -269,11 +378,13 @@ void pool_max_fwd(hipStream_t s, const float* x, int N, int C, int H, int W,
     hipLaunchKernelGGL(k_pool_max_fwd3, dim3(nblocks(total, 2)), dim3(TPB),
                        0, s, x, N, C, H, W, ph, pw, sh, sw, OH, OW, y,
                        mask);
+    ktrace(kPoolMaxFwd, kVarK3);
     return;
   }
   hipLaunchKernelGGL(k_pool_max_fwd, dim3(nblocks(total, 2)), dim3(TPB), 0,
                      s, x, N, C, H, W, kh, kw, ph, pw, sh, sw, OH, OW, y,
                      mask);
+  ktrace(kPoolMaxFwd, kVarGeneric);
 }
 
 // deterministic gather backward: each input element scans the <= ceil(k/s)^2
@@ -433,23 +544,27 @@ void pool_max_bwd(hipStream_t s, const float* dy, const int* mask, int N,
     hipLaunchKernelGGL(k_pool_max_bwd3s1, dim3(nblocks(total, 2)),
                        dim3(TPB), 0, s, dy, mask, N, C, H, W, ph, pw, OH,
                        OW, dx);
+    ktrace(kPoolMaxBwd, kVarK3S1);
     return;
   }
   if (kh == 3 && kw == 3 && sh == 2 && sw == 2) {
     hipLaunchKernelGGL(k_pool_max_bwd3s2, dim3(nblocks(total, 2)),
                        dim3(TPB), 0, s, dy, mask, N, C, H, W, ph, pw, OH,
                        OW, dx);
+    ktrace(kPoolMaxBwd, kVarK3S2);
     return;
   }
   if (kh == 3 && kw == 3) {
     hipLaunchKernelGGL(k_pool_max_bwd3, dim3(nblocks(total, 2)), dim3(TPB),
                        0, s, dy, mask, N, C, H, W, ph, pw, sh, sw, OH, OW,
                        dx);
+    ktrace(kPoolMaxBwd, kVarK3);
     return;
   }
   hipLaunchKernelGGL(k_pool_max_bwd, dim3(nblocks(total, 2)), dim3(TPB), 0,
                      s, dy, mask, N, C, H, W, kh, kw, ph, pw, sh, sw, OH,
                      OW, dx);
+  ktrace(kPoolMaxBwd, kVarGeneric);
 }
 
 __global__ void k_pool_ave_fwd(const float* __restrict__ x, int N, int C,
@@ -482,6 +597,7 @@ void pool_ave_fwd(hipStream_t s, const float* x, int N, int C, int H, int W,
   PerfScope perf(PERF_CLASS("pool"), s, 0, 4.0 * total * (kh * kw + 1));
   hipLaunchKernelGGL(k_pool_ave_fwd, dim3(nblocks(total, 2)), dim3(TPB), 0,
                      s, x, N, C, H, W, kh, kw, ph, pw, sh, sw, OH, OW, y);
+  ktrace(kPoolAveFwd);
 }
 
 __global__ void k_pool_ave_bwd(const float* __restrict__ dy, int N, int C,
@@ -516,6 +632,7 @@ void pool_ave_bwd(hipStream_t s, const float* dy, int N, int C, int H, int W,
   PerfScope perf(PERF_CLASS("pool"), s, 0, 8.0 * total);
   hipLaunchKernelGGL(k_pool_ave_bwd, dim3(nblocks(total, 2)), dim3(TPB), 0,
                      s, dy, N, C, H, W, kh, kw, ph, pw, sh, sw, OH, OW, dx);
+  ktrace(kPoolAveBwd);
 }
 
 // y = x * a[c] (+ b[c]) — Scale layer forward (b = bias or null) and its
@@ -656,10 +773,12 @@ void bn_fwd_stats(hipStream_t s, const float* x, int N, int C, long S,
     hipLaunchKernelGGL(k_bn_fwd_stats_v4, dim3(C * nb), dim3(TPB), 0, s,
                        (const f4*)x, N, C, (int)(S / 4), nb,
                        (double2*)partials);
+    ktrace_bn(kBnFwdStats, kVarV4, N, nb, (int)(S / 4));
     return;
   }
   hipLaunchKernelGGL(k_bn_fwd_stats, dim3(C * nb), dim3(TPB), 0, s, x, N, C,
                      S, nb, (double2*)partials);
+  ktrace_bn(kBnFwdStats, kVarScalar, N, nb, S);
 }
 
 __global__ void k_bn_fwd_finalize(const double2* __restrict__ partials,
@@ -931,11 +1050,13 @@ void bn_bwd_stats(hipStream_t s, const float* x, const float* dy,
                        (const f4*)x, (const f4*)dy, mean, inv_std, N, C,
                        (int)(S / 4), nb, scale, bias, frelu,
                        (double2*)partials);
+    ktrace_bn(kBnBwdStats, kVarV4, N, nb, (int)(S / 4));
     return;
   }
   hipLaunchKernelGGL(k_bn_bwd_stats, dim3(C * nb), dim3(TPB), 0, s, x, dy,
                      mean, inv_std, N, C, S, nb, scale, bias, frelu,
                      (double2*)partials);
+  ktrace_bn(kBnBwdStats, kVarScalar, N, nb, S);
 }
 
 __global__ void k_bn_bwd_finalize(const double2* __restrict__ partials,
@@ -1158,11 +1279,13 @@ void lrn_fwd(hipStream_t s, const float* x, int N, int C, int H, int W,
     hipLaunchKernelGGL(k_lrn_fwd_t<5>, dim3(nblocks((N * S + 1) / 2)),
                        dim3(TPB), 0, s, x, N, C, S, alpha / size, beta, k,
                        scale, y);
+    ktrace(kLrnFwd, kVarRing5, (N * S) & 1);
     return;
   }
   hipLaunchKernelGGL(k_lrn_fwd, dim3(nblocks((N * S + 1) / 2)), dim3(TPB),
                      0, s, x, N, C, S, size, alpha / size, beta, k, scale,
                      y);
+  ktrace(kLrnFwd, kVarGeneric, (N * S) & 1);
 }
 
 __global__ void k_lrn_bwd(const float* __restrict__ x,
@@ -1287,11 +1410,13 @@ void lrn_bwd(hipStream_t s, const float* x, const float* y, const float* dy,
     hipLaunchKernelGGL(k_lrn_bwd_t<5>, dim3(nblocks((N * S + 1) / 2)),
                        dim3(TPB), 0, s, x, y, dy, scale, N, C, S,
                        2.f * alpha * beta / size, beta, dx);
+    ktrace(kLrnBwd, kVarRing5, (N * S) & 1);
     return;
   }
   hipLaunchKernelGGL(k_lrn_bwd, dim3(nblocks(N * S)), dim3(TPB), 0, s, x, y,
                      dy, scale, N, C, S, size, 2.f * alpha * beta / size,
                      beta, dx);
+  ktrace(kLrnBwd, kVarGeneric, (N * S) & 1);
 }
 
 // ------------------------------------------------------------ softmax
@@ -1345,6 +1470,7 @@ void softmax_fwd(hipStream_t s, const float* x, int outer, int C, int inner,
   const int blocks = (int)std::min<long>((rows + 3) / 4, 2048);
   hipLaunchKernelGGL(k_softmax_fwd, dim3(blocks), dim3(TPB), 0, s, x, outer,
                      C, inner, prob);
+  ktrace(kSoftmaxFwd, kVarNone, rows, C, blocks);
 }
 
 // two-stage deterministic loss sum: block partials then final add
@@ -1630,6 +1756,7 @@ void sgd_update_segmented(hipStream_t s, long lo, long hi, float* g_arena,
   hipLaunchKernelGGL(k_sgd_seg, dim3(nblocks(hi - lo, 4)), dim3(TPB), 0, s,
                      lo, hi, g_arena, h_arena, seg_off, w_ptrs, lr_mults,
                      decay_mults, nseg, mom, lr, decay, gscale);
+  ktrace(kSgdSeg, kVarNone, lo, hi, nseg);
 }
 
 // ---------------------------------------------------- LMDB transform

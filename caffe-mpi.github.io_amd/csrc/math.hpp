@@ -95,6 +95,22 @@ void gemm(hipStream_t s, bool transA, bool transB, long M, long N, long K,
 void gemm_trace(bool enable);
 long gemm_trace_read(char* buf, long cap);
 
+// Variant trace of the elementwise launch wrappers (pooling, BN statistics,
+// LRN, softmax, segmented SGD): which specialised kernel a call launched and
+// the numbers that shape it.  Same contract as gemm_trace: off by default,
+// enabling clears the log, at most 4096 records, one "key=value ..." line
+// per record:
+//   op=pool_max_fwd var=k3|generic
+//   op=pool_max_bwd var=k3s1|k3s2|k3|generic
+//   op=pool_ave_fwd          op=pool_ave_bwd
+//   op=bn_fwd_stats|bn_bwd_stats var=v4|scalar nb=<slices> span_max=<largest
+//       per-block span, in elements (scalar) or float4 packs (v4)>
+//   op=lrn_fwd|lrn_bwd var=ring5|generic odd=<(N*H*W) & 1>
+//   op=softmax_fwd rows=<outer*inner> C=<C> blocks=<grid>
+//   op=sgd_seg lo=<lo> hi=<hi> nseg=<nseg>
+void kernel_trace(bool enable);
+long kernel_trace_read(char* buf, long cap);
+
 // db[c] = Σ_n Σ_s dy[n][c][s] (deterministic)
 void bias_grad(hipStream_t s, const float* dy, int N, int C, long S,
                float* db);

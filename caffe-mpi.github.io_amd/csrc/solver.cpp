@@ -198,6 +198,12 @@ void Reducer::flush(hipEvent_t ev) {
     }
     // bucket-fused update: one launch over the flat arena range
     S.ensure_seg_table();
+    // the kernel writes the weights through the table's cached pointers,
+    // behind the blobs' backs: mark each blob's device copy as the newer
+    // one, or a host copy made by an earlier read (param get, snapshot)
+    // would be served again, stale, after this update
+    for (long k = bucket_start_; k < bucket_end_; ++k)
+      params[k].blob->mutable_gpu_data();
     gpu::sgd_update_segmented(
         E.comm_stream, first.offset, first.offset + count,
         S.net().diff_arena(), S.history(), S.d_seg_off_, S.d_w_ptrs_,

@@ -159,6 +159,14 @@ int caffe_perf_reset(void);
  * a first call of cap 0. */
 int caffe_gemm_trace(int enable);
 int caffe_gemm_trace_read(char* buf, int cap);
+/* Kernel variant trace (off by default), same contract as the GEMM route
+ * trace: while enabled, the pooling, BatchNorm-statistics, LRN, softmax and
+ * segmented-SGD launch wrappers record one line per call, e.g.
+ * "op=pool_max_bwd var=k3s1", "op=bn_fwd_stats var=v4 nb=2 span_max=1056",
+ * "op=lrn_fwd var=ring5 odd=1", "op=softmax_fwd rows=8450 C=3 blocks=2048",
+ * "op=sgd_seg lo=0 hi=272 nseg=6". */
+int caffe_kernel_trace(int enable);
+int caffe_kernel_trace_read(char* buf, int cap);
 
 #ifdef __cplusplus
 }

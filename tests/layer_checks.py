@@ -161,9 +161,30 @@ def check_pool(mode, pool="MAX", N=2, C=4, H=13, W=13, k=3, s=2, p=0):
 
 
 def check_pool_bwd(mode, pool="MAX", N=2, C=4, H=13, W=13, k=3, s=2,
-                   p=0):
+                   p=0, kernel_h=None, kernel_w=None, stride_h=None,
+                   stride_w=None, pad_h=None, pad_w=None, x=None, errs=None):
+    """kernel_h/w, stride_h/w, pad_h/w: per-axis geometry (each defaults to
+    k / s / p; giving any of them writes the per-axis prototxt fields).
+    x: the input, when the caller needs a particular one (e.g. full of
+    ties).  errs receives the measured relerr of y / dx before each is
+    asserted.  Returns x, dy, the oracle's mask (MAX) and dx, and the
+    engine's dx, for checks beyond the relerr bound."""
+    errs = {} if errs is None else errs
+    per_axis = any(v is not None for v in (kernel_h, kernel_w, stride_h,
+                                           stride_w, pad_h, pad_w))
+    kh = k if kernel_h is None else kernel_h
+    kw = k if kernel_w is None else kernel_w
+    sh = s if stride_h is None else stride_h
+    sw = s if stride_w is None else stride_w
+    ph = p if pad_h is None else pad_h
+    pw = p if pad_w is None else pad_w
+    geom = (f"kernel_h: {kh} kernel_w: {kw} stride_h: {sh} stride_w: {sw} "
+            f"pad_h: {ph} pad_w: {pw}" if per_axis
+            else f"kernel_size: {k} stride: {s} pad: {p}")
     # pool preceded by a 1x1 conv so prop_down[0] is true
-    x = rng.standard_normal((N, C, H, W)).astype(np.float32)
+    if x is None:
+        x = rng.standard_normal((N, C, H, W)).astype(np.float32)
+    assert x.shape == (N, C, H, W) and x.dtype == np.float32
     w = np.eye(C, dtype=np.float32).reshape(C, C, 1, 1).copy()
     body = f"""layer {{
   name: "c1"
@@ -177,29 +198,54 @@ layer {{
   type: "Pooling"
   bottom: "mid"
   top: "out"
-  pooling_param {{ pool: {pool} kernel_size: {k} stride: {s} pad: {p} }}
+  pooling_param {{ pool: {pool} {geom} }}
 }}"""
+    mask = None
     if pool == "MAX":
-        y_ref, mask = orc.pool_max_fwd(x, k, k, p, p, s, s)
+        y_ref, mask = orc.pool_max_fwd(x, kh, kw, ph, pw, sh, sw)
     else:
-        y_ref = orc.pool_ave_fwd(x, k, k, p, p, s, s)
+        y_ref = orc.pool_ave_fwd(x, kh, kw, ph, pw, sh, sw)
     dy = rng.standard_normal(y_ref.shape).astype(np.float32)
     net, y = run_layer(mode, [(N, C, H, W)], body, [x], params=[w],
                        top_diff=dy)
-    assert relerr(y, y_ref) < TOL
+    errs["y"] = relerr(y, y_ref)
+    assert errs["y"] < TOL, f"pool {pool} fwd {errs['y']}"
     if pool == "MAX":
         dx_ref = orc.pool_max_bwd(dy, mask, H, W)
     else:
-        dx_ref = orc.pool_ave_bwd(dy, H, W, k, k, p, p, s, s)
+        dx_ref = orc.pool_ave_bwd(dy, H, W, kh, kw, ph, pw, sh, sw)
     # dx lands in "mid"'s diff == conv's top diff; identity conv passes it on
-    assert relerr(net.blob("mid", diff=True), dx_ref) < TOL
+    dx = net.blob("mid", diff=True)
+    errs["dx"] = relerr(dx, dx_ref)
+    assert errs["dx"] < TOL, f"pool {pool} dx {errs['dx']}"
+    return dict(x=x, dy=dy, mask=mask, dx_ref=dx_ref, dx=dx)
 
 
-def check_bn(mode, N=4, C=6, H=5, W=5, scale_bias=True):
-    x = rng.standard_normal((N, C, H, W)).astype(np.float32)
-    sc = (rng.standard_normal(C) + 1.5).astype(np.float32)
-    bi = rng.standard_normal(C).astype(np.float32)
-    eps = 1e-4
+def bn_inputs(r, N, C, H, W, mean=0.0, std=1.0):
+    """check_bn's x, scale, bias and dy, drawn from the generator r."""
+    x = r.standard_normal((N, C, H, W)).astype(np.float32)
+    if mean != 0.0 or std != 1.0:
+        x = (x * np.float32(std) + np.float32(mean)).astype(np.float32)
+    sc = (r.standard_normal(C) + 1.5).astype(np.float32)
+    bi = r.standard_normal(C).astype(np.float32)
+    dy = r.standard_normal(x.shape).astype(np.float32)
+    return x, sc, bi, dy
+
+
+def check_bn(mode, N=4, C=6, H=5, W=5, scale_bias=True, mean=0.0, std=1.0,
+             eps=1e-4, seed=None, errs=None):
+    """mean, std: of the normal input.  seed: draw the inputs from a
+    generator of their own, bn_inputs(default_rng(seed), ...), so that a
+    test can restate them.  errs receives the measured relerr of y / dx /
+    dscale / dbias before each is asserted.
+
+    The default input (unit variance, eps 1e-4) cannot see eps: the oracle
+    with eps = 0 differs from the true output by relerr 3.7e-5, below TOL.
+    test_kernel_variants.py adds a std 0.01 case, where it gives 0.42."""
+    errs = {} if errs is None else errs
+    x, sc, bi, dy = bn_inputs(rng if seed is None
+                              else np.random.default_rng(seed),
+                              N, C, H, W, mean, std)
     body = f"""layer {{
   name: "bn"
   type: "BatchNorm"
@@ -211,44 +257,73 @@ def check_bn(mode, N=4, C=6, H=5, W=5, scale_bias=True):
     scale_bias: {"true" if scale_bias else "false"}
   }}
 }}"""
-    y_ref, mean, var, inv_std, xnorm = orc.bn_fwd_train(
+    y_ref, _, _, inv_std, xnorm = orc.bn_fwd_train(
         x, eps, sc if scale_bias else None, bi if scale_bias else None)
-    dy = rng.standard_normal(y_ref.shape).astype(np.float32)
     # learnable params of BN are [scale, bias] (stats blobs skipped)
     params = [sc, bi] if scale_bias else None
     net, y = run_layer(mode, [(N, C, H, W)], body, [x], params=params,
                        top_diff=dy)
-    assert relerr(y, y_ref) < TOL, f"bn fwd {relerr(y, y_ref)}"
+    errs["y"] = relerr(y, y_ref)
+    assert errs["y"] < TOL, f"bn fwd {errs['y']}"
     dx_ref, dsc_ref, dbi_ref = orc.bn_bwd(xnorm, dy, inv_std,
                                           sc if scale_bias else None)
-    assert relerr(net.blob("in0", diff=True), dx_ref) < TOL, "bn dx"
+    errs["dx"] = relerr(net.blob("in0", diff=True), dx_ref)
+    assert errs["dx"] < TOL, f"bn dx {errs['dx']}"
     if scale_bias:
         # learnable params (arena order): scale=idx 0, bias=idx 1 of this
         # layer; BN stats blobs are skipped (skip_apply_update)
-        assert relerr(net.param(0, diff=True), dsc_ref) < TOL, "bn dscale"
-        assert relerr(net.param(1, diff=True), dbi_ref) < TOL, "bn dbias"
+        errs["dscale"] = relerr(net.param(0, diff=True), dsc_ref)
+        assert errs["dscale"] < TOL, f"bn dscale {errs['dscale']}"
+        errs["dbias"] = relerr(net.param(1, diff=True), dbi_ref)
+        assert errs["dbias"] < TOL, f"bn dbias {errs['dbias']}"
 
 
-def check_relu(mode, n=1000):
-    x = rng.standard_normal((2, 5, 10, 10)).astype(np.float32)
-    body = """layer {
+def check_relu(mode, n=1000, shape=(2, 5, 10, 10), negative_slope=0.0,
+               errs=None):
+    errs = {} if errs is None else errs
+    C = shape[1]
+    x = rng.standard_normal(shape).astype(np.float32)
+    rp = (f" relu_param {{ negative_slope: {negative_slope} }}"
+          if negative_slope else "")
+    body = f"""layer {{
   name: "c1"
   type: "Convolution"
   bottom: "in0"
   top: "mid"
-  convolution_param { num_output: 5 kernel_size: 1 bias_term: false }
-}
-layer { name: "r" type: "ReLU" bottom: "mid" top: "out" }"""
-    w = np.eye(5, dtype=np.float32).reshape(5, 5, 1, 1).copy()
-    y_ref = orc.relu_fwd(x)
+  convolution_param {{ num_output: {C} kernel_size: 1 bias_term: false }}
+}}
+layer {{ name: "r" type: "ReLU" bottom: "mid" top: "out"{rp} }}"""
+    w = np.eye(C, dtype=np.float32).reshape(C, C, 1, 1).copy()
+    y_ref = orc.relu_fwd(x, negative_slope)
     dy = rng.standard_normal(x.shape).astype(np.float32)
     net, y = run_layer(mode, [x.shape], body, [x], params=[w], top_diff=dy)
-    assert relerr(y, y_ref) < TOL
-    assert relerr(net.blob("mid", diff=True), orc.relu_bwd(x, dy)) < TOL
+    errs["y"] = relerr(y, y_ref)
+    assert errs["y"] < TOL, f"relu fwd {errs['y']}"
+    errs["dx"] = relerr(net.blob("mid", diff=True),
+                        orc.relu_bwd(x, dy, negative_slope))
+    assert errs["dx"] < TOL, f"relu dx {errs['dx']}"
 
 
-def check_lrn(mode, N=2, C=8, H=6, W=6, size=5, alpha=1e-4, beta=0.75):
-    x = rng.standard_normal((N, C, H, W)).astype(np.float32)
+def lrn_inputs(r, N, C, H, W):
+    """check_lrn's x and dy, drawn from the generator r."""
+    x = r.standard_normal((N, C, H, W)).astype(np.float32)
+    dy = r.standard_normal(x.shape).astype(np.float32)
+    return x, dy
+
+
+def check_lrn(mode, N=2, C=8, H=6, W=6, size=5, alpha=1e-4, beta=0.75,
+              seed=None, errs=None):
+    """seed: as in check_bn, with lrn_inputs.
+
+    The default alpha = 1e-4 on unit-normal input gives scale ~ 1.0001,
+    so the case barely sees the window: the oracle with local_size 3 in
+    place of 5 differs from the true output by relerr 1.05e-4 forward and
+    1.2e-4 backward, and y = x by 1.8e-4, against TOL = 1e-4.
+    test_kernel_variants.py runs every LRN shape at alpha = 1.0, where the
+    same perturbation gives 0.24."""
+    errs = {} if errs is None else errs
+    x, dy = lrn_inputs(rng if seed is None else np.random.default_rng(seed),
+                       N, C, H, W)
     w = np.eye(C, dtype=np.float32).reshape(C, C, 1, 1).copy()
     body = f"""layer {{
   name: "c1"
@@ -265,14 +340,16 @@ layer {{
   lrn_param {{ local_size: {size} alpha: {alpha} beta: {beta} }}
 }}"""
     y_ref, scale = orc.lrn_fwd(x, size, alpha, beta)
-    dy = rng.standard_normal(x.shape).astype(np.float32)
     net, y = run_layer(mode, [x.shape], body, [x], params=[w], top_diff=dy)
-    assert relerr(y, y_ref) < TOL
+    errs["y"] = relerr(y, y_ref)
+    assert errs["y"] < TOL, f"lrn fwd {errs['y']}"
     dx_ref = orc.lrn_bwd(x, y_ref, dy, scale, size, alpha, beta)
-    assert relerr(net.blob("mid", diff=True), dx_ref) < TOL
+    errs["dx"] = relerr(net.blob("mid", diff=True), dx_ref)
+    assert errs["dx"] < TOL, f"lrn dx {errs['dx']}"
 
 
-def check_softmaxloss(mode, N=8, C=10):
+def check_softmaxloss(mode, N=8, C=10, errs=None):
+    errs = {} if errs is None else errs
     x = (rng.standard_normal((N, C)) * 3).astype(np.float32)
     lab = rng.integers(0, C, N).astype(np.float32)
     body = """layer {
@@ -294,13 +371,16 @@ layer {
     loss_ref = orc.softmaxloss_fwd(prob, lab, N, C, 1)
     net, y = run_layer(mode, [(N, C), (N,)], body, [x, lab],
                        params=[w, np.zeros(C, np.float32)])
-    assert abs(y[0] - loss_ref) < 1e-5 * max(1, abs(loss_ref))
+    errs["loss"] = abs(y[0] - loss_ref) / max(1, abs(loss_ref))
+    assert abs(y[0] - loss_ref) < 1e-5 * max(1, abs(loss_ref)), errs["loss"]
     net.backward()
     dx_ref = orc.softmaxloss_bwd(prob, lab, N, C, 1)
-    assert relerr(net.blob("fc", diff=True), dx_ref) < TOL
+    errs["dx"] = relerr(net.blob("fc", diff=True), dx_ref)
+    assert errs["dx"] < TOL, f"softmaxloss dx {errs['dx']}"
 
 
-def check_softmaxloss_spatial(mode, N=2, C=5, H=3, W=4):
+def check_softmaxloss_spatial(mode, N=2, C=5, H=3, W=4, errs=None):
+    errs = {} if errs is None else errs
     # FCN-style spatial loss: inner = H*W > 1 exercises the inner-stride
     # walk of the softmax/NLL kernels (softmax_layer.cu's inner_num_ path)
     x = (rng.standard_normal((N, C, H, W)) * 2).astype(np.float32)
@@ -316,10 +396,13 @@ def check_softmaxloss_spatial(mode, N=2, C=5, H=3, W=4):
   top: "out"
 }"""
     net, y = run_layer(mode, [(N, C, H, W), (N, H, W)], body, [x, lab])
-    assert abs(y.ravel()[0] - loss_ref) < 1e-5 * max(1, abs(loss_ref))
+    errs["loss"] = abs(y.ravel()[0] - loss_ref) / max(1, abs(loss_ref))
+    assert abs(y.ravel()[0] - loss_ref) < 1e-5 * max(1, abs(loss_ref)), \
+        errs["loss"]
     net.backward()
     dx_ref = orc.softmaxloss_bwd(prob, lab.ravel(), N, C, inner)
-    assert relerr(net.blob("in0", diff=True), dx_ref) < TOL
+    errs["dx"] = relerr(net.blob("in0", diff=True), dx_ref)
+    assert errs["dx"] < TOL, f"softmaxloss spatial dx {errs['dx']}"
 
 
 def check_eltwise_concat(mode):
