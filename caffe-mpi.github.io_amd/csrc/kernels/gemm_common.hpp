@@ -1,10 +1,14 @@
 // gemm_common.hpp — shared pieces of the MFMA GEMM family (fp32 + bf16):
-// the kernel argument block and the 16-element operand reader that
+// the kernel argument block, the 16-element operand reader that
 // understands plain, channel-view and implicit-im2col-view addressing
-// (strides included).  See gemm_f32.hip for the design notes.
+// (strides included), and the kernel parts every family member uses (tile
+// swizzle, split-K range, accumulator epilogue, K-waves combine).  See
+// gemm_f32.hip for the design notes.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../layers.hpp"
 
@@ -149,6 +153,141 @@ __device__ __forceinline__ void read16(const float* __restrict__ P, long r,
 #pragma unroll
     for (int j = 0; j < 16; ++j) out[j] = j < nvalid ? p[j] : 0.f;
   }
+}
+
+// ---- kernel parts shared by every GEMM kernel (fp32, slim, bf16, wide)
+
+// Tile of this block.  Bijective XCD-aware swizzle
+// (cdna_hip_programming.md T1): contiguous tile chunks per XCD so
+// neighbouring tiles share L2-resident panels.
+__device__ __forceinline__ void tile_origin(const GemmArgs& g, long& tile_m,
+                                            long& tile_n) {
+  long flat = blockIdx.x;
+  const long nwg = g.tiles;
+  const long q = nwg / 8, rr = nwg % 8;
+  const long xcd = flat % 8, idx = flat / 8;
+  flat = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
+  tile_m = flat / g.tn;
+  tile_n = flat - tile_m * g.tn;
+}
+
+// K range of split-K slice blockIdx.z; starts BK-aligned so read16 chunks
+// stay 16-aligned.  False when the slice is empty (cannot happen for
+// SK <= ceil(K / 4BK)).
+template <int BK>
+__device__ __forceinline__ bool splitk_range(const GemmArgs& g, long& k_lo,
+                                             long& k_hi) {
+  const int sk = blockIdx.z;
+  k_lo = g.K * sk / g.SK / BK * BK;
+  k_hi = (sk == g.SK - 1) ? g.K : g.K * (sk + 1) / g.SK / BK * BK;
+  return k_lo < k_hi;
+}
+
+// Epilogue of one 32x32 MFMA accumulator whose first row is row0; col is
+// this lane's column.  C/D map: col = lane&31, acc reg r holds row
+// (r&3) + 8*(r>>2) + 4*ksel with ksel = lane>>5 (handed in: the kernels
+// hold it already, and deriving it from threadIdx again here made
+// k_gemm_bf16, which sits at 256 VGPRs, spill 8 bytes/lane more —
+// DESIGN.md §8, "GEMM helper forms").  Split-K blocks store alpha*acc
+// into their slab; otherwise bias, ReLU and beta are applied in that order
+// and the value goes to C (plain, NCHW scatter or strided scatter).
+template <bool SPLITK>
+__device__ __forceinline__ void store_acc(const GemmArgs& g, const f32x16& a,
+                                          long row0, long col, int ksel) {
+  if (col >= g.N) return;
+  // col is constant across the 16 regs — hoist the scatter division
+  long col_base = 0;  // n*n_stride + pix for scatter, col for plain
+  bool col_ok = true;
+  if (!SPLITK && g.spad > 0) {
+    const long n = col / g.spad;
+    const long sp = col - n * g.spad;
+    col_ok = sp < g.S;  // padded scatter column: no destination
+    long pix = sp;
+    if (g.OWo > 0) {  // strided scatter (1x1/s2 dgrad)
+      const int oh = (int)(sp / g.OWo);
+      const int ow = (int)(sp - (long)oh * g.OWo);
+      pix = ((long)oh * g.osh) * g.Wd + (long)ow * g.osw;
+    }
+    col_base = n * g.n_stride + pix;
+  }
+  if (!col_ok) return;
+  const float cbias =
+      (!SPLITK && g.bias && g.bias_per_col) ? g.bias[col] : 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const long row = row0 + ((r & 3) + 8 * (r >> 2) + 4 * ksel);
+    if (row >= g.M) continue;
+    float v = g.alpha * a[r];
+    if (SPLITK) {
+      g.slab[((long)blockIdx.z * g.M + row) * g.N + col] = v;
+      continue;
+    }
+    if (g.bias) v += g.bias_per_col ? cbias : g.bias[row];
+    if (g.relu) v = fmaxf(v, 0.f);
+    const long off =
+        g.spad > 0 ? col_base + row * g.Srow : row * g.ldc + col;
+    if (g.beta != 0.f) v += g.beta * g.C[off];
+    g.C[off] = v;
+  }
+}
+
+// K-waves combine of the 128-tile kernels: the waves with wk > 0 hold
+// K-range partials of output sub-tile `sub` (= wc*mwaves + wr).  They park
+// their accumulators in the (now idle) staging LDS and the wk == 0 wave
+// adds them in ascending wk order — deterministic.  False for the parked
+// waves, which are done.  The wave coordinates are handed in, not derived
+// from threadIdx again: the kernels hold them, and re-deriving them moved
+// the register allocation of the K-loops.
+__device__ __forceinline__ bool kwaves_combine(float* lds, int lane, int wave,
+                                               int wk, int sub, int mn,
+                                               int kwaves, f32x16& acc00,
+                                               f32x16& acc01, f32x16& acc10,
+                                               f32x16& acc11) {
+  __syncthreads();  // all reads of the staging buffers are done
+  if (wk > 0) {
+    float* slot = lds + (long)(wave - mn) * 4096 + lane * 64;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      slot[r] = acc00[r];
+      slot[16 + r] = acc01[r];
+      slot[32 + r] = acc10[r];
+      slot[48 + r] = acc11[r];
+    }
+  }
+  __syncthreads();
+  if (wk > 0) return false;
+  for (int k2 = 1; k2 < kwaves; ++k2) {
+    const int src_wave = k2 * mn + sub;
+    const float* slot = lds + (long)(src_wave - mn) * 4096 + lane * 64;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc00[r] += slot[r];
+      acc01[r] += slot[16 + r];
+      acc10[r] += slot[32 + r];
+      acc11[r] += slot[48 + r];
+    }
+  }
+  return true;
+}
+
+// Runtime (transA, transB, splitk) -> template arguments: calls
+// f(TA, TB, SPLITK) with std::bool_constant values.  transA && transB has
+// no caller and no instantiation.
+template <class F>
+void with_gemm_variant(bool ta, bool tb, bool splitk, F&& f) {
+  CHECK_(!(ta && tb)) << "transA && transB has no kernel";
+  auto with_sk = [&](auto TA, auto TB) {
+    if (splitk)
+      f(TA, TB, std::true_type{});
+    else
+      f(TA, TB, std::false_type{});
+  };
+  if (ta)
+    with_sk(std::true_type{}, std::false_type{});
+  else if (tb)
+    with_sk(std::false_type{}, std::true_type{});
+  else
+    with_sk(std::false_type{}, std::false_type{});
 }
 
 }  // namespace gpu

@@ -74,11 +74,9 @@ struct GemmView {
                        // conv1 7x7s2, the 1x1s2 projections, AlexNet s4)
 };
 
-// Wt[ci][co*kh*kw + ki*kw + kj] = W[co][ci][kh-1-ki][kw-1-kj] — the
-// flipped/transposed weights that turn backward-data into a forward
+// Wt[ci][co*kh*kw + ki*kw + kj] = W[co][ci][kh-1-ki][kw-1-kj] per group —
+// the flipped/transposed weights that turn backward-data into a forward
 // convolution over dY (s1 only)
-void weight_flip(hipStream_t s, const float* w, int Cout, int Cin, int kh,
-                 int kw, float* wt);
 void weight_flip_grouped(hipStream_t s, const float* w, int Cout, int Cin_g,
                          int kh, int kw, int groups, float* wt);
 

@@ -57,6 +57,16 @@ CONV_CASES = {
         "fam=slim64 ta=1 tb=0 sk=1 M=40 N=288 K=48 tm=1 tn=3 bv=chan "
         "epi=scatter",
     ]),
+    # case A with 24 input channels: the dgrad is the 32-row slim tile with
+    # a transposed A (staged by threads 0..63 only) and the NCHW scatter
+    "A24": (dict(N=2, C=24, H=5, W=27, Co=48, k=1, s=1, p=0), [
+        "fam=slim64 ta=0 tb=0 sk=1 M=48 N=288 K=24 tm=1 tn=3 bv=chan "
+        "epi=scatter bias=row",
+        "fam=f32_128 ta=0 tb=1 sk=3 kw=4 M=48 N=24 K=288 tm=1 tn=1 av=chan "
+        "bv=chan epi=none",
+        "fam=slim32 ta=1 tb=0 sk=1 M=24 N=288 K=48 tm=1 tn=2 bv=chan "
+        "epi=scatter",
+    ]),
     # 128-tile with the implicit-im2col B view + scatter, M tail 80 of 128;
     # dgrad via flipped weights and the transposed-geometry view
     "B": (dict(N=2, C=72, H=5, W=27, Co=80, k=3, s=1, p=1), [
@@ -249,6 +259,14 @@ IP_CASES = {
         "bias=col",
         "fam=f32_128 ta=1 tb=0 sk=1 kw=4 M=48 N=24 K=72 tm=1 tn=1 epi=none",
         "fam=f32_128 ta=0 tb=0 sk=1 kw=2 M=72 N=24 K=48 tm=1 tn=1 epi=none",
+    ]),
+    # wgrad on the 32-row slim tile with a transposed A and split-K; dgrad
+    # slim64 by the remainder rule
+    "ip_300_200_24": (dict(M=300, K=200, Nout=24), [
+        "fam=f32_128 ta=0 tb=1 sk=1 kw=2 M=300 N=24 K=200 tm=3 tn=1 "
+        "epi=plain bias=col",
+        "fam=slim32 ta=1 tb=0 sk=3 M=24 N=200 K=300 tm=1 tn=1 epi=none",
+        "fam=slim64 ta=0 tb=0 sk=1 M=300 N=200 K=24 tm=5 tn=2 epi=none",
     ]),
     # split-K reduce, scalar kernel: wgrad M*N = 37*53 is odd
     "ip_300_53_37": (dict(M=300, K=53, Nout=37), [
