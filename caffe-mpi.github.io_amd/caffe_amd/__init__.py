@@ -80,6 +80,11 @@ _lib.caffe_net_param_info.argtypes = [_vp, ctypes.c_int, ctypes.c_char_p,
 _lib.caffe_net_param_get.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _f32p,
                                      ctypes.c_long]
 _lib.caffe_net_param_set.argtypes = [_vp, ctypes.c_int, _f32p, ctypes.c_long]
+_lib.caffe_solver_type.argtypes = [_vp]
+_lib.caffe_solver_type.restype = ctypes.c_char_p
+_lib.caffe_solver_history_slots.argtypes = [_vp]
+_lib.caffe_solver_history.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _f32p,
+                                      ctypes.c_long]
 
 ALLREDUCE_CB = ctypes.CFUNCTYPE(None, _f32p, ctypes.c_long, ctypes.c_void_p)
 _lib.caffe_comm_set_callback.argtypes = [_vp, ALLREDUCE_CB, ctypes.c_void_p,
@@ -195,19 +200,22 @@ def _trace_records(read):
 
 def kernel_trace(enable):
     """Record which specialised kernel the pooling, BatchNorm-statistics,
-    LRN, softmax and segmented-SGD launch wrappers pick (off by default;
-    enabling clears the log, which holds 4096 records)."""
+    LRN, softmax and segmented solver-update launch wrappers pick (off by
+    default; enabling clears the log, which holds 4096 records)."""
     _ck(_lib.caffe_kernel_trace(1 if enable else 0))
 
 
 def kernel_trace_read():
     """The recorded launches in call order, one dict per wrapper call:
     op (pool_max_fwd | pool_max_bwd | pool_ave_fwd | pool_ave_bwd |
-    bn_fwd_stats | bn_bwd_stats | lrn_fwd | lrn_bwd | softmax_fwd | sgd_seg)
-    and, by op: var (k3 | k3s1 | k3s2 | generic for max pooling, v4 | scalar
-    for BN, ring5 | generic for LRN); nb and span_max (BN batch slices and
-    the largest per-block span); odd (LRN: N*H*W is odd); rows, C, blocks
-    (softmax); lo, hi, nseg (SGD bucket range in the param arena)."""
+    bn_fwd_stats | bn_bwd_stats | lrn_fwd | lrn_bwd | softmax_fwd | sgd_seg |
+    solver_seg) and, by op: var (k3 | k3s1 | k3s2 | generic for max pooling,
+    v4 | scalar for BN, ring5 | generic for LRN); nb and span_max (BN batch
+    slices and the largest per-block span); odd (LRN: N*H*W is odd); rows,
+    C, blocks (softmax); lo, hi, nseg (update bucket range in the param
+    arena: sgd_seg for SGD with L2, solver_seg for every other solver type
+    and for L1, which adds rule (sgd | nesterov | adagrad | rmsprop |
+    adadelta | adam) and reg (L1 | L2))."""
     return _trace_records(_lib.caffe_kernel_trace_read)
 
 
@@ -311,6 +319,25 @@ class Solver:
 
     def loss(self):
         return _lib.caffe_solver_loss(self._h)
+
+    @property
+    def type(self):
+        """The solver's registry name: SGD | Nesterov | AdaGrad | RMSProp |
+        AdaDelta | Adam (a deprecated solver_type enum is mapped onto it)."""
+        return _lib.caffe_solver_type(self._h).decode()
+
+    @property
+    def history_slots(self):
+        """History blobs per param: 2 for AdaDelta and Adam, else 1."""
+        return _lib.caffe_solver_history_slots(self._h)
+
+    def history(self, i, slot=0):
+        """History slot `slot` of param i (indexed as Net.param)."""
+        _, _, cnt = self.net.param_info(i)
+        out = np.empty(cnt, np.float32)
+        _ck(_lib.caffe_solver_history(self._h, slot, i,
+                                      out.ctypes.data_as(_f32p), cnt))
+        return out
 
     def comm_unique_id(self):
         buf = (ctypes.c_uint8 * 128)()

@@ -7,7 +7,9 @@ pycaffe.py).  A script written against classic pycaffe —
     net.blobs['data'].data[...] = x
     net.forward(); net.backward()
     w = net.params['conv1'][0].data
-    solver = caffe.SGDSolver(solver_proto)
+    solver = caffe.SGDSolver(solver_proto)       # or NesterovSolver,
+    # AdaGradSolver, RMSPropSolver, AdaDeltaSolver, AdamSolver, or
+    # caffe.get_solver(solver_proto) for whichever the file's type names
     solver.step(100); solver.net.blobs['loss'].data
 
 — runs against this engine by `import caffe_amd.pycaffe as caffe`.
@@ -189,11 +191,21 @@ class Net:
 
 
 class SGDSolver:
-    """caffe.SGDSolver(prototxt) — Solver::Step semantics."""
+    """caffe.SGDSolver(prototxt) — Solver::Step semantics.  The other five
+    solver classes below share every method; each accepts only a file of
+    its own type (an absent type means SGD)."""
 
-    def __init__(self, path):
+    _type = "SGD"
+
+    def __init__(self, path, _solver=None):
         self._solver_path = path
-        self._solver = _Solver(path=path)
+        self._solver = _solver if _solver is not None else _Solver(path=path)
+        if self._solver.type != self._type:
+            got = self._solver.type
+            _lib.caffe_solver_free(self._solver._h)
+            raise CaffeError(
+                f"{type(self).__name__} takes a solver of type "
+                f"\"{self._type}\", but {path} has type \"{got}\"")
         self.net = _WrappedSolverNet(self._solver)
 
     def step(self, iters):
@@ -221,6 +233,37 @@ class SGDSolver:
     @property
     def iter(self):
         return self._solver.iter
+
+
+class NesterovSolver(SGDSolver):
+    _type = "Nesterov"
+
+
+class AdaGradSolver(SGDSolver):
+    _type = "AdaGrad"
+
+
+class RMSPropSolver(SGDSolver):
+    _type = "RMSProp"
+
+
+class AdaDeltaSolver(SGDSolver):
+    _type = "AdaDelta"
+
+
+class AdamSolver(SGDSolver):
+    _type = "Adam"
+
+
+def get_solver(path):
+    """caffe.get_solver(prototxt): the solver class that the file's type
+    names (reference _caffe.cpp GetSolverFromFile -> SolverRegistry)."""
+    solver = _Solver(path=path)
+    for cls in (SGDSolver, NesterovSolver, AdaGradSolver, RMSPropSolver,
+                AdaDeltaSolver, AdamSolver):
+        if cls._type == solver.type:
+            return cls(path, _solver=solver)
+    raise CaffeError(f"no solver class for type \"{solver.type}\"")
 
 
 class _WrappedSolverNet(Net):

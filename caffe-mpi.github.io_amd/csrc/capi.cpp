@@ -183,6 +183,20 @@ int caffe_solver_restore(caffe_solver_t s, const char* state_path) {
   API_CATCH
 }
 
+const char* caffe_solver_type(caffe_solver_t s) { return S(s)->type(); }
+
+int caffe_solver_history_slots(caffe_solver_t s) {
+  return S(s)->history_slots();
+}
+
+int caffe_solver_history(caffe_solver_t s, int slot, int param_index,
+                         float* out, long count) {
+  API_TRY
+  S(s)->copy_history(slot, param_index, out, count);
+  return 0;
+  API_CATCH
+}
+
 int caffe_net_save_weights(caffe_net_t n, const char* path) {
   API_TRY
   N(n)->SaveWeights(path);

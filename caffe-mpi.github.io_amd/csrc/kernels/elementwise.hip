@@ -36,7 +36,7 @@ static inline int nblocks(long n, int per_thread = 1) {
 // launches, so the log cannot disagree with what ran.
 enum KOp {
   kPoolMaxFwd, kPoolMaxBwd, kPoolAveFwd, kPoolAveBwd, kBnFwdStats,
-  kBnBwdStats, kLrnFwd, kLrnBwd, kSoftmaxFwd, kSgdSeg
+  kBnBwdStats, kLrnFwd, kLrnBwd, kSoftmaxFwd, kSgdSeg, kSolverSeg
 };
 enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
             kVarScalar, kVarRing5 };
@@ -86,7 +86,10 @@ long kernel_trace_read(char* buf, long cap) {
   static const char* const op[] = {
       "pool_max_fwd", "pool_max_bwd", "pool_ave_fwd", "pool_ave_bwd",
       "bn_fwd_stats", "bn_bwd_stats", "lrn_fwd",      "lrn_bwd",
-      "softmax_fwd",  "sgd_seg"};
+      "softmax_fwd",  "sgd_seg",      "solver_seg"};
+  // solver_seg keeps rule * 2 + l1 in the var byte
+  static const char* const rule[] = {"sgd",     "nesterov", "adagrad",
+                                     "rmsprop", "adadelta", "adam"};
   static const char* const var[] = {"",        "k3", "k3s1",   "k3s2",
                                     "generic", "v4", "scalar", "ring5"};
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
@@ -118,6 +121,12 @@ long kernel_trace_read(char* buf, long cap) {
       case kSoftmaxFwd:
         n = snprintf(line, sizeof(line), "op=%s rows=%ld C=%ld blocks=%ld\n",
                      op[r.op], r.a, r.b, r.c);
+        break;
+      case kSolverSeg:
+        n = snprintf(line, sizeof(line),
+                     "op=%s rule=%s reg=%s lo=%ld hi=%ld nseg=%ld\n",
+                     op[r.op], rule[r.var >> 1], (r.var & 1) ? "L1" : "L2",
+                     r.a, r.b, r.c);
         break;
       default:
         n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld\n",
@@ -1757,6 +1766,103 @@ void sgd_update_segmented(hipStream_t s, long lo, long hi, float* g_arena,
                      lo, hi, g_arena, h_arena, seg_off, w_ptrs, lr_mults,
                      decay_mults, nseg, mom, lr, decay, gscale);
   ktrace(kSgdSeg, kVarNone, lo, hi, nseg);
+}
+
+// segmented fused update for the other solver rules (and SGD with L1): the
+// k_sgd_seg contract — one launch per bucket over the arena range, segment
+// tables uploaded once, per-iteration coefficients as kernel arguments, no
+// atomics (each element belongs to one thread: deterministic) — but
+// float4-wide.  lo4/hi4 count 4-float packs; arena offsets and padded counts
+// are multiples of 16 floats and blob memory is 64B-padded, so a pack never
+// straddles a segment, the weight pack is 16B-aligned and in bounds, and
+// the binary search runs once per pack.
+// Pad lanes have g == 0 and w == 0 (blob memory is zero-filled past count),
+// so gr == 0 there for L2 and L1 alike, and from a zeroed history every rule
+// leaves them finite: the quotients are 0 / (0 + delta) with delta > 0
+// (AdaGrad, RMSProp, Adam) or 0 * sqrt(delta / delta) (AdaDelta).
+template <int Rule, bool kL1>
+__global__ void k_solver_seg(long lo4, long hi4, f4* __restrict__ g_arena,
+                             f4* __restrict__ h_arena,
+                             f4* __restrict__ h2_arena,
+                             const long* __restrict__ seg_off,
+                             float* const* __restrict__ w_ptrs,
+                             const float* __restrict__ lr_mults,
+                             const float* __restrict__ decay_mults, int nseg,
+                             SolverCoef c) {
+  constexpr bool kTwo = Rule == kRuleAdaDelta || Rule == kRuleAdam;
+  for (long p = lo4 + blockIdx.x * (long)blockDim.x + threadIdx.x; p < hi4;
+       p += (long)gridDim.x * blockDim.x) {
+    const long i = 4 * p;
+    // binary search: largest k with seg_off[k] <= i
+    int a = 0, b = nseg - 1;
+    while (a < b) {
+      const int m = (a + b + 1) >> 1;
+      if (seg_off[m] <= i)
+        a = m;
+      else
+        b = m - 1;
+    }
+    f4* wp = (f4*)(w_ptrs[a] + (i - seg_off[a]));
+    const float lr = c.lr * lr_mults[a];
+    const float decay = c.decay * decay_mults[a];
+    const f4 gv = g_arena[p];
+    f4 wv = *wp, hv = h_arena[p];
+    f4 h2v = {0.f, 0.f, 0.f, 0.f};
+    if (kTwo) h2v = h2_arena[p];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float hj = hv[j], h2j = h2v[j];
+      wv[j] -= solver_rule_step<Rule, kL1>(gv[j], wv[j], hj, h2j, c, lr,
+                                           decay);
+      hv[j] = hj;
+      h2v[j] = h2j;
+    }
+    *wp = wv;
+    h_arena[p] = hv;
+    if (kTwo) h2_arena[p] = h2v;
+    g_arena[p] = f4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+void solver_update_segmented(hipStream_t s, int rule, bool l1, long lo,
+                             long hi, float* g_arena, float* h_arena,
+                             float* h2_arena, const long* seg_off,
+                             float* const* w_ptrs, const float* lr_mults,
+                             const float* decay_mults, int nseg,
+                             const SolverCoef& coef) {
+  CHECK_(lo % 4 == 0 && hi % 4 == 0)
+      << "solver_update_segmented: range [" << lo << ", " << hi
+      << ") is not float4-aligned";
+  CHECK_(rule >= 0 && rule < kNumSolverRules) << "bad solver rule " << rule;
+  const int slots = solver_rule_slots(rule);
+  CHECK_(slots == 1 || h2_arena) << "rule " << rule << " needs two slots";
+  if (hi <= lo) return;
+  PerfScope perf(PERF_CLASS("solver"), s, 0,
+                 (16.0 + 8.0 * slots) * (hi - lo));
+  const long lo4 = lo / 4, hi4 = hi / 4;
+  const dim3 grid(nblocks(hi4 - lo4)), block(TPB);
+#define SOLVER_SEG_LAUNCH(R)                                                \
+  case R:                                                                   \
+    if (l1)                                                                 \
+      hipLaunchKernelGGL((k_solver_seg<R, true>), grid, block, 0, s, lo4,   \
+                         hi4, (f4*)g_arena, (f4*)h_arena, (f4*)h2_arena,    \
+                         seg_off, w_ptrs, lr_mults, decay_mults, nseg,      \
+                         coef);                                             \
+    else                                                                    \
+      hipLaunchKernelGGL((k_solver_seg<R, false>), grid, block, 0, s, lo4,  \
+                         hi4, (f4*)g_arena, (f4*)h_arena, (f4*)h2_arena,    \
+                         seg_off, w_ptrs, lr_mults, decay_mults, nseg,      \
+                         coef);                                             \
+    break;
+  switch (rule) {
+    SOLVER_SEG_LAUNCH(kRuleSgd)
+    SOLVER_SEG_LAUNCH(kRuleNesterov)
+    SOLVER_SEG_LAUNCH(kRuleAdaGrad)
+    SOLVER_SEG_LAUNCH(kRuleRmsProp)
+    SOLVER_SEG_LAUNCH(kRuleAdaDelta)
+    SOLVER_SEG_LAUNCH(kRuleAdam)
+  }
+#undef SOLVER_SEG_LAUNCH
+  ktrace(kSolverSeg, rule * 2 + (l1 ? 1 : 0), lo, hi, nseg);
 }
 
 // ---------------------------------------------------- LMDB transform

@@ -6,6 +6,8 @@
 // caller's stream.
 #pragma once
 
+#include <cmath>
+
 #include "core.hpp"
 
 namespace camd {
@@ -29,6 +31,68 @@ inline int conv_out_dim(int in, int k, int pad, int stride, int dil) {
 }
 void pool_out_dim(int H, int W, int kh, int kw, int ph, int pw, int sh,
                   int sw, int* OH, int* OW);  // ceil + clip, pooling_layer.cpp:86
+
+// ------------------------------------------------------ solver update rules
+// The reference's six solver types (solvers/*_solver.{cpp,cu}; registry names
+// SGD, Nesterov, AdaGrad, RMSProp, AdaDelta, Adam).  One per-element function
+// serves the CPU loops (solver.cpp) and the GPU kernel (k_solver_seg), so the
+// two modes cannot drift apart.
+enum SolverRule {
+  kRuleSgd = 0, kRuleNesterov, kRuleAdaGrad, kRuleRmsProp, kRuleAdaDelta,
+  kRuleAdam, kNumSolverRules
+};
+inline int solver_rule_slots(int rule) {
+  return rule == kRuleAdaDelta || rule == kRuleAdam ? 2 : 1;
+}
+// per-iteration coefficients, passed by value as kernel arguments; lr and
+// decay are the solver-wide values (per-param multipliers come from tables)
+struct SolverCoef {
+  float mom;     // momentum (Adam: beta1)
+  float lr;      // cur lr (Adam: times the bias correction of this iteration)
+  float decay;   // weight_decay
+  float gscale;  // 1 / (world * iter_size), applied before any square
+  float aux;     // RMSProp: rms_decay; Adam: momentum2 (beta2)
+  float delta;   // the rule's clamped delta (0 where the rule has none)
+};
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define CAMD_HD __host__ __device__
+#else
+#define CAMD_HD
+#endif
+// One element of one rule: reads the raw reduced gradient g and the weight
+// w, updates the history slot(s) in place and returns the value to subtract
+// from w.  lr and decay already carry the param's multipliers.
+template <int Rule, bool kL1>
+CAMD_HD inline float solver_rule_step(float g, float w, float& h, float& h2,
+                                      const SolverCoef& c, float lr,
+                                      float decay) {
+  const float reg = kL1 ? (float)((0.f < w) - (w < 0.f)) : w;
+  const float gr = g * c.gscale + reg * decay;
+  if (Rule == kRuleSgd) {
+    h = c.mom * h + lr * gr;
+    return h;
+  } else if (Rule == kRuleNesterov) {
+    const float h0 = h;
+    h = c.mom * h0 + lr * gr;
+    return (1.f + c.mom) * h - c.mom * h0;
+  } else if (Rule == kRuleAdaGrad) {
+    h += gr * gr;
+    return lr * gr / (sqrtf(h) + c.delta);
+  } else if (Rule == kRuleRmsProp) {
+    h = c.aux * h + (1.f - c.aux) * gr * gr;
+    return lr * gr / (sqrtf(h) + c.delta);
+  } else if (Rule == kRuleAdaDelta) {
+    h = c.mom * h + (1.f - c.mom) * gr * gr;
+    const float u = gr * sqrtf((h2 + c.delta) / (h + c.delta));
+    h2 = c.mom * h2 + (1.f - c.mom) * u * u;
+    return lr * u;
+  } else {  // kRuleAdam: h = m, h2 = v
+    h = c.mom * h + (1.f - c.mom) * gr;
+    h2 = c.aux * h2 + (1.f - c.aux) * gr * gr;
+    return lr * h / (sqrtf(h2) + c.delta);
+  }
+}
 
 // ------------------------------------------------------------ GPU launchers
 namespace gpu {
@@ -106,6 +170,8 @@ long gemm_trace_read(char* buf, long cap);
 //   op=lrn_fwd|lrn_bwd var=ring5|generic odd=<(N*H*W) & 1>
 //   op=softmax_fwd rows=<outer*inner> C=<C> blocks=<grid>
 //   op=sgd_seg lo=<lo> hi=<hi> nseg=<nseg>
+//   op=solver_seg rule=<sgd|nesterov|adagrad|rmsprop|adadelta|adam>
+//       reg=<L1|L2> lo=<lo> hi=<hi> nseg=<nseg>
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
 
@@ -229,6 +295,19 @@ void sgd_update_segmented(hipStream_t s, long lo, long hi, float* g_arena,
                           float* const* w_ptrs, const float* lr_mults,
                           const float* decay_mults, int nseg, float mom,
                           float lr, float decay, float gscale);
+
+// segmented fused update for every rule but plain SGD+L2 (which stays on
+// sgd_update_segmented): same contract — one launch per bucket over the flat
+// arena range [lo, hi), segment tables uploaded once, coefficients as kernel
+// arguments — but float4-wide, so lo and hi must be multiples of 4 (arena
+// offsets and padded counts are multiples of 16).  h2_arena is the second
+// history slot (AdaDelta, Adam); nullptr for the one-slot rules.
+void solver_update_segmented(hipStream_t s, int rule, bool l1, long lo,
+                             long hi, float* g_arena, float* h_arena,
+                             float* h2_arena, const long* seg_off,
+                             float* const* w_ptrs, const float* lr_mults,
+                             const float* decay_mults, int nseg,
+                             const SolverCoef& coef);
 
 // LMDB batch transform: uint8 -> fp32 crop/mirror/mean/scale
 // (data_transformer.cu:14-100 analog); geo = per-image (ho, wo, mirror),

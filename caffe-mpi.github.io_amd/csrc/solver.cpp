@@ -9,7 +9,113 @@
 
 namespace camd {
 
+namespace {
+// registry names (reference SolverRegistry) and the deprecated enum idents
+// (caffe.proto:288-295), both indexed by SolverRule
+const char* const kTypeNames[kNumSolverRules] = {
+    "SGD", "Nesterov", "AdaGrad", "RMSProp", "AdaDelta", "Adam"};
+const char* const kEnumNames[kNumSolverRules] = {
+    "SGD", "NESTEROV", "ADAGRAD", "RMSPROP", "ADADELTA", "ADAM"};
+
+// CPU-mode update of one param for every rule but SGD+L2 (whose loop stays
+// in Reducer::flush): the per-element rule the GPU kernel runs
+template <int Rule, bool kL1>
+void cpu_rule_loop(long n, float* g, float* w, float* h, float* h2,
+                   const SolverCoef& c, float lr, float decay) {
+  float unused = 0.f;
+  for (long i = 0; i < n; ++i) {
+    w[i] -= solver_rule_step<Rule, kL1>(g[i], w[i], h[i],
+                                        h2 ? h2[i] : unused, c, lr, decay);
+    g[i] = 0.f;
+  }
+}
+void cpu_rule_update(int rule, bool l1, long n, float* g, float* w, float* h,
+                     float* h2, const SolverCoef& c, float lr, float decay) {
+#define CPU_RULE(R)                                              \
+  case R:                                                        \
+    if (l1)                                                      \
+      cpu_rule_loop<R, true>(n, g, w, h, h2, c, lr, decay);      \
+    else                                                         \
+      cpu_rule_loop<R, false>(n, g, w, h, h2, c, lr, decay);     \
+    break;
+  switch (rule) {
+    CPU_RULE(kRuleSgd)
+    CPU_RULE(kRuleNesterov)
+    CPU_RULE(kRuleAdaGrad)
+    CPU_RULE(kRuleRmsProp)
+    CPU_RULE(kRuleAdaDelta)
+    CPU_RULE(kRuleAdam)
+  }
+#undef CPU_RULE
+}
+}  // namespace
+
+// type / regularization_type and the rule's constants, checked once
+// (reference: SolverRegistry::CreateSolver, the constructor_sanity_check of
+// adagrad/rmsprop in sgd_solvers.hpp, upgrade_proto.cpp:1003 for the
+// deprecated solver_type enum)
+void Solver::parse_type() {
+  const PMsg& sp = *param_;
+  if (sp.has("type") && sp.has("solver_type"))
+    CAMD_FATAL << "solver gives both type: \"" << sp.str("type")
+               << "\" and the deprecated solver_type: "
+               << sp.str("solver_type") << " — give type only";
+  rule_ = -1;
+  if (sp.has("solver_type")) {
+    const std::string st = sp.str("solver_type");
+    for (int r = 0; r < kNumSolverRules; ++r)
+      // text format takes the enum by name or by number
+      if (st == kEnumNames[r] || st == std::to_string(r)) rule_ = r;
+    if (rule_ < 0)
+      CAMD_FATAL << "unknown solver_type: " << st
+                 << " (SGD | NESTEROV | ADAGRAD | RMSPROP | ADADELTA | ADAM)";
+  } else {
+    const std::string t = sp.str("type", "SGD");
+    for (int r = 0; r < kNumSolverRules; ++r)
+      if (t == kTypeNames[r]) rule_ = r;
+    if (rule_ < 0)
+      CAMD_FATAL << "unknown solver type: \"" << t
+                 << "\" (SGD | Nesterov | AdaGrad | RMSProp | AdaDelta | Adam)";
+  }
+  type_name_ = kTypeNames[rule_];
+  const std::string reg = sp.str("regularization_type", "L2");
+  if (reg != "L1" && reg != "L2")
+    CAMD_FATAL << "unknown regularization_type: \"" << reg
+               << "\" (L1 | L2)";
+  l1_ = reg == "L1";
+  const float delta = (float)sp.num("delta", 1e-8);  // caffe.proto:272
+  if ((rule_ == kRuleAdaGrad || rule_ == kRuleRmsProp) &&
+      sp.num("momentum", 0.0) != 0.0)
+    CAMD_FATAL << type_name_ << " solver requires momentum == 0, got momentum: "
+               << sp.str("momentum");
+  // the delta floors are the reference's own (solvers/*_solver.cpp)
+  switch (rule_) {
+    case kRuleAdaGrad:
+      delta_ = std::max(delta, 1e-3f);
+      break;
+    case kRuleRmsProp: {
+      const double rho = sp.num("rms_decay", 0.0);  // caffe.proto:278
+      if (!(rho >= 0.0 && rho < 1.0))
+        CAMD_FATAL << "RMSProp solver requires 0 <= rms_decay < 1, got "
+                      "rms_decay: " << sp.str("rms_decay");
+      aux_ = (float)rho;
+      delta_ = std::max(delta, 1e-4f);
+      break;
+    }
+    case kRuleAdaDelta:
+      delta_ = std::max(delta, 1e-3f);
+      break;
+    case kRuleAdam:
+      aux_ = (float)sp.num("momentum2", 0.999);  // caffe.proto:274
+      delta_ = std::max(delta, 1e-4f);
+      break;
+    default:
+      break;
+  }
+}
+
 Solver::Solver(const PMsgPtr& sp, int batch_override) : param_(sp) {
+  parse_type();
   PMsgPtr net_msg;
   if (sp->has("net")) {
     net_msg = parse_prototxt_file(sp->str("net"));
@@ -37,14 +143,26 @@ Solver::Solver(const PMsgPtr& sp, int batch_override) : param_(sp) {
     HIP_CHECK(hipMemsetAsync(history_, 0,
                              sizeof(float) * net_->learnable_count(),
                              E.stream));
+    if (history_slots() == 2) {
+      history2_ =
+          (float*)E.dalloc.alloc(sizeof(float) * net_->learnable_count());
+      HIP_CHECK(hipMemsetAsync(history2_, 0,
+                               sizeof(float) * net_->learnable_count(),
+                               E.stream));
+    }
   } else if (nparams > 0) {
     host_history_.assign(net_->learnable_count(), 0.f);
+    if (history_slots() == 2)
+      host_history2_.assign(net_->learnable_count(), 0.f);
   }
 }
 
 Solver::~Solver() {
   if (history_)
     Engine::get().dalloc.release(history_,
+                                 sizeof(float) * net_->learnable_count());
+  if (history2_)
+    Engine::get().dalloc.release(history2_,
                                  sizeof(float) * net_->learnable_count());
   if (acc_)
     Engine::get().dalloc.release(acc_,
@@ -204,11 +322,17 @@ void Reducer::flush(hipEvent_t ev) {
     // would be served again, stale, after this update
     for (long k = bucket_start_; k < bucket_end_; ++k)
       params[k].blob->mutable_gpu_data();
-    gpu::sgd_update_segmented(
-        E.comm_stream, first.offset, first.offset + count,
-        S.net().diff_arena(), S.history(), S.d_seg_off_, S.d_w_ptrs_,
-        S.d_lrs_, S.d_decays_, (int)params.size(), S.cur_mom_, S.cur_lr_,
-        S.weight_decay_, S.grad_scale_);
+    if (S.rule_ == kRuleSgd && !S.l1_)
+      gpu::sgd_update_segmented(
+          E.comm_stream, first.offset, first.offset + count,
+          S.net().diff_arena(), S.history(), S.d_seg_off_, S.d_w_ptrs_,
+          S.d_lrs_, S.d_decays_, (int)params.size(), S.cur_mom_, S.cur_lr_,
+          S.weight_decay_, S.grad_scale_);
+    else
+      gpu::solver_update_segmented(
+          E.comm_stream, S.rule_, S.l1_, first.offset, first.offset + count,
+          S.net().diff_arena(), S.history(0), S.history(1), S.d_seg_off_,
+          S.d_w_ptrs_, S.d_lrs_, S.d_decays_, (int)params.size(), S.coef());
   } else {
     if (S.comm_ && S.comm_->world() > 1) {
       // CPU buckets: gather the param diffs into one flat range is
@@ -224,6 +348,14 @@ void Reducer::flush(hipEvent_t ev) {
       float* h = S.host_history().data() + p.offset;
       const float lr = S.cur_lr_ * p.lr_mult;
       const float decay = S.weight_decay_ * p.decay_mult;
+      if (S.rule_ != kRuleSgd || S.l1_) {
+        float* h2 = S.history_slots() == 2
+                        ? S.host_history(1).data() + p.offset
+                        : nullptr;
+        cpu_rule_update(S.rule_, S.l1_, p.count, g, w, h, h2, S.coef(),
+                        S.upd_lr_ * p.lr_mult, decay);
+        continue;
+      }
       for (long i = 0; i < p.count; ++i) {
         float gi = g[i] * S.grad_scale_ + decay * w[i];
         gi = h[i] = S.cur_mom_ * h[i] + lr * gi;
@@ -288,6 +420,15 @@ void Solver::Step(int iters) {
       TestAll(test_iter);
     cur_lr_ = GetLearningRate();
     cur_mom_ = GetMomentum();
+    upd_lr_ = cur_lr_;
+    if (rule_ == kRuleAdam) {
+      // bias correction at t = iter_ + 1, in float, once per iteration and
+      // folded into the rate (adam_solver.cpp:42-43); iter_ comes back from
+      // Restore, so a resumed run continues the same sequence
+      const float t = (float)(iter_ + 1);
+      upd_lr_ *= std::sqrt(1.f - std::pow(aux_, t)) /
+                 (1.f - std::pow(cur_mom_, t));
+    }
     const float world =
         comm_ && comm_->world() > 1 ? (float)comm_->world() : 1.f;
     grad_scale_ = 1.f / (world * (float)iter_size);
@@ -331,6 +472,25 @@ void Solver::Step(int iters) {
     perf_iters_ += done_iters;
   } else {
     skipped_iters_ += done_iters;
+  }
+}
+
+void Solver::copy_history(int slot, int param_index, float* out, long count) {
+  CHECK_(slot >= 0 && slot < history_slots())
+      << "history slot " << slot << " of this " << type_name_ << " solver ("
+      << history_slots() << " slots)";
+  auto& params = net_->learnable_params();
+  CHECK_(param_index >= 0 && param_index < (int)params.size())
+      << "param index " << param_index;
+  const auto& p = params[param_index];
+  CHECK_LE_(count, p.count);
+  Engine& E = Engine::get();
+  if (E.mode == Mode::GPU) {
+    E.sync();  // the updates run on comm_stream
+    HIP_CHECK(hipMemcpy(out, history(slot) + p.offset, sizeof(float) * count,
+                        hipMemcpyDeviceToHost));
+  } else {
+    memcpy(out, host_history(slot).data() + p.offset, sizeof(float) * count);
   }
 }
 
@@ -430,26 +590,29 @@ void Solver::Snapshot() {
   std::vector<float> host;
   // history blobs go out in FORWARD learnable-param order — the order the
   // reference writes (sgd_solver.cpp:262-353); the arena itself is
-  // reverse-layer order, so walk the permutation
+  // reverse-layer order, so walk the permutation.  The two-slot rules
+  // write slot 0 of every param, then slot 1 of every param — the
+  // reference's history_[i + N] (adam_solver.cpp:37-39)
   auto& aparams = net_->learnable_params();
-  for (int pi : net_->forward_param_order()) {
-    const auto& p = aparams[pi];
-    wire::Writer bw;
-    if (E.mode == Mode::GPU) {
-      host.resize(p.count);
-      HIP_CHECK(hipMemcpy(host.data(), history_ + p.offset,
-                          sizeof(float) * p.count, hipMemcpyDeviceToHost));
-      bw.packed_floats(5, host.data(), p.count);
-    } else {
-      bw.packed_floats(5, host_history_.data() + p.offset, p.count);
+  for (int slot = 0; slot < history_slots(); ++slot)
+    for (int pi : net_->forward_param_order()) {
+      const auto& p = aparams[pi];
+      wire::Writer bw;
+      if (E.mode == Mode::GPU) {
+        host.resize(p.count);
+        HIP_CHECK(hipMemcpy(host.data(), history(slot) + p.offset,
+                            sizeof(float) * p.count, hipMemcpyDeviceToHost));
+        bw.packed_floats(5, host.data(), p.count);
+      } else {
+        bw.packed_floats(5, host_history(slot).data() + p.offset, p.count);
+      }
+      wire::Writer shw;
+      std::vector<int64_t> dims(p.blob->shape().begin(),
+                                p.blob->shape().end());
+      shw.packed_i64(1, dims);
+      bw.submsg(7, shw.out);
+      sw.submsg(3, bw.out);
     }
-    wire::Writer shw;
-    std::vector<int64_t> dims(p.blob->shape().begin(),
-                              p.blob->shape().end());
-    shw.packed_i64(1, dims);
-    bw.submsg(7, shw.out);
-    sw.submsg(3, bw.out);
-  }
   sw.vint(4, current_step_);
   {
     const auto dir = std::filesystem::path(state).parent_path();
@@ -475,21 +638,36 @@ void Solver::Restore(const std::string& path) {
   // the wire carries history in forward learnable-param order (reference
   // sgd_solver.cpp:307-353) — map each blob back to its arena slot
   const std::vector<int> order = net_->forward_param_order();
+  const size_t nparams = order.size();
+  if (rule_ != kRuleSgd) {
+    // the other solvers take exactly slots * N blobs (reference
+    // sgd_solver.cpp RestoreSolverStateFromBinaryProto); checked before
+    // anything is overwritten
+    size_t nhist = 0;
+    wire::Reader count_r(buf.data(), buf.size());
+    while (count_r.next(&fld))
+      if (fld.num == 3 && fld.wt == 2) ++nhist;
+    if (nhist != (size_t)history_slots() * nparams)
+      CAMD_FATAL << "Incorrect length of history blobs: " << path << " has "
+                 << nhist << ", this " << type_name_ << " solver of "
+                 << nparams << " params takes " << history_slots() * nparams;
+  }
   while (r.next(&fld)) {
     if (fld.num == 1 && fld.wt == 0) iter_ = (long)fld.vint;
     else if (fld.num == 2 && fld.wt == 2) learned.assign(fld.data, fld.len);
     else if (fld.num == 4 && fld.wt == 0) current_step_ = (int)fld.vint;
     else if (fld.num == 3 && fld.wt == 2) {
       auto b = wire::parse_blob(fld.data, fld.len);
-      CHECK_LT_(hidx, order.size());
-      const auto& p = params[order[hidx]];
+      CHECK_LT_(hidx, nparams * history_slots());
+      const int slot = (int)(hidx / nparams);
+      const auto& p = params[order[hidx % nparams]];
       CHECK_EQ_((long)b.data.size(), p.count);
       if (E.mode == Mode::GPU) {
-        HIP_CHECK(hipMemcpy(history_ + p.offset, b.data.data(),
+        HIP_CHECK(hipMemcpy(history(slot) + p.offset, b.data.data(),
                             sizeof(float) * b.data.size(),
                             hipMemcpyHostToDevice));
       } else {
-        memcpy(host_history_.data() + p.offset, b.data.data(),
+        memcpy(host_history(slot).data() + p.offset, b.data.data(),
                sizeof(float) * b.data.size());
       }
       ++hidx;

@@ -1,7 +1,9 @@
-// solver.hpp — SGD solver + the bucketed gradient reducer.
+// solver.hpp — the solver (SGD, Nesterov, AdaGrad, RMSProp, AdaDelta, Adam)
+// + the bucketed gradient reducer.
 //
 // Reference semantics: solver.cpp Step :187-353, sgd_solver.cpp lr/momentum
-// policies :24-91 and fused update :143-149 / sgd_solver.cu:10-20;
+// policies :24-91 and fused update :143-149 / sgd_solver.cu:10-20; the other
+// update rules solvers/{nesterov,adagrad,rmsprop,adadelta,adam}_solver.*;
 // Net::ReduceAndUpdate bucketing net.cpp:757-877 (reduce_buckets default 6,
 // caffe.proto:140).  MI355X re-design: the reduce thread is replaced by
 // launch-chaining — each bucket's ncclAllReduce (RCCL over xGMI) and the
@@ -82,6 +84,15 @@ class Solver {
     net_->LoadWeights(model_path);
   }
   long iter() const { return iter_; }
+  // SolverParameter.type (caffe.proto:269), with the deprecated solver_type
+  // enum mapped onto it (upgrade_proto.cpp:1003)
+  const char* type() const { return type_name_; }
+  int rule() const { return rule_; }
+  bool l1() const { return l1_; }
+  int history_slots() const { return solver_rule_slots(rule_); }
+  // copies history slot `slot` of learnable param `param_index` (arena
+  // order, as Net::learnable_params) to out, from the device or the host
+  void copy_history(int slot, int param_index, float* out, long count);
   float last_loss() { return net_->loss(); }
   const PMsgPtr& param() const { return param_; }
 
@@ -98,14 +109,22 @@ class Solver {
 
   void set_comm(std::unique_ptr<Comm> c) { comm_ = std::move(c); }
   Comm* comm() { return comm_.get(); }
-  float* history() { return history_; }
-  std::vector<float>& host_history() { return host_history_; }
+  float* history(int slot = 0) { return slot ? history2_ : history_; }
+  std::vector<float>& host_history(int slot = 0) {
+    return slot ? host_history2_ : host_history_;
+  }
   void bcast_weights();  // initial weight broadcast (parallel.cpp:208-227)
 
   // per-iteration cached coefficients for the fused update
   float cur_lr_ = 0.f, cur_mom_ = 0.f, weight_decay_ = 0.f;
   float grad_scale_ = 1.f;
+  // cur_lr_ for the update: Adam folds this iteration's bias correction in
+  float upd_lr_ = 0.f;
   long bucket_budget_ = 0;  // elements per bucket
+  SolverCoef coef() const {
+    return SolverCoef{cur_mom_, upd_lr_, weight_decay_, grad_scale_, aux_,
+                      delta_};
+  }
 
  private:
   PMsgPtr param_;
@@ -121,6 +140,16 @@ class Solver {
   mutable int current_step_ = 0;
   float* history_ = nullptr;  // device arena, diff-arena layout
   std::vector<float> host_history_;
+  // second history slot (AdaDelta, Adam only): same layout, zero-filled
+  float* history2_ = nullptr;
+  std::vector<float> host_history2_;
+  // the update rule, parsed once at construction
+  int rule_ = kRuleSgd;
+  bool l1_ = false;
+  const char* type_name_ = "SGD";
+  float aux_ = 0.f;    // RMSProp rms_decay / Adam momentum2
+  float delta_ = 0.f;  // the rule's clamped delta
+  void parse_type();
   // device segment table for the bucket-fused update (GPU mode): arena
   // offsets, per-param weight base pointers, lr/decay (mults folded in at
   // flush time by scaling the per-iteration coefficients)

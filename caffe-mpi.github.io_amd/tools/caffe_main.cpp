@@ -202,6 +202,7 @@ static int run_train_rank(std::map<std::string, std::string> flags, int dev,
                              (local_rank < total % local_world ? 1 : 0));
   }
   Solver solver(sp, batch_override);
+  if (grank == 0) fprintf(stderr, "Solver type: %s\n", solver.type());
   solver.set_action_request(&action_request);
   if (grank != 0) solver.set_snapshot_enabled(false);
   if (gworld > 1) {

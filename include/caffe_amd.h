@@ -64,7 +64,9 @@ caffe_solver_t caffe_solver_create_from_text(const char* solver_prototxt,
                                              int batch_override);
 void caffe_solver_free(caffe_solver_t s);
 /* Solver::Step(iters) (solver.cpp:187-353): forward, backward with the
- * bucketed all-reduce overlapped on the side stream, fused SGD update */
+ * bucketed all-reduce overlapped on the side stream, fused update by the
+ * solver's rule (ComputeUpdateValue of sgd_solver.cpp and the five
+ * solvers beside it) */
 int caffe_solver_step(caffe_solver_t s, int iters);
 long caffe_solver_iter(caffe_solver_t s);
 /* current net loss (the reference additionally smooths over the display
@@ -77,6 +79,20 @@ caffe_net_t caffe_solver_net(caffe_solver_t s);
  * weights + .solverstate with SGD history, sgd_solver.cpp:262-353) */
 int caffe_solver_snapshot(caffe_solver_t s);
 int caffe_solver_restore(caffe_solver_t s, const char* state_path);
+/* Solver::type() (solver.hpp, the SolverRegistry name: "SGD", "Nesterov",
+ * "AdaGrad", "RMSProp", "AdaDelta" or "Adam"; SolverParameter.type,
+ * caffe.proto:269, with the deprecated solver_type enum mapped onto it,
+ * upgrade_proto.cpp:1003).  The string lives as long as the library. */
+const char* caffe_solver_type(caffe_solver_t s);
+/* history blobs per learnable param: SGDSolver::history() holds N blobs,
+ * AdaDelta and Adam append N more (AdaDeltaPreSolve / AdamPreSolve,
+ * adam_solver.cpp:8-16) — 1 or 2 */
+int caffe_solver_history_slots(caffe_solver_t s);
+/* SGDSolver::history()[param_index + slot * N] (sgd_solvers.hpp), copied
+ * out of device or host memory; param_index as in caffe_net_param_get,
+ * count <= the param's element count — syncs */
+int caffe_solver_history(caffe_solver_t s, int slot, int param_index,
+                         float* out, long count);
 /* Net weight interop (net.cpp:1055-1248) */
 int caffe_net_save_weights(caffe_net_t n, const char* path);
 int caffe_net_load_weights(caffe_net_t n, const char* path);
@@ -164,7 +180,9 @@ int caffe_gemm_trace_read(char* buf, int cap);
  * segmented-SGD launch wrappers record one line per call, e.g.
  * "op=pool_max_bwd var=k3s1", "op=bn_fwd_stats var=v4 nb=2 span_max=1056",
  * "op=lrn_fwd var=ring5 odd=1", "op=softmax_fwd rows=8450 C=3 blocks=2048",
- * "op=sgd_seg lo=0 hi=272 nseg=6". */
+ * "op=sgd_seg lo=0 hi=272 nseg=6"; the segmented update of the other solver
+ * rules (and SGD with L1) records
+ * "op=solver_seg rule=adam reg=L2 lo=0 hi=272 nseg=6". */
 int caffe_kernel_trace(int enable);
 int caffe_kernel_trace_read(char* buf, int cap);
 
