@@ -67,6 +67,8 @@ _lib.caffe_set_random_seed.argtypes = [ctypes.c_uint64]
 _lib.caffe_set_compute.argtypes = [ctypes.c_char_p]
 _lib.caffe_gemm_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_kernel_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
+_lib.caffe_fastdiv_selftest.argtypes = [ctypes.c_uint, ctypes.c_uint]
+_lib.caffe_fastdiv_selftest.restype = ctypes.c_long
 
 _f32p = ctypes.POINTER(ctypes.c_float)
 _lib.caffe_net_blob_get.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int,
@@ -181,6 +183,24 @@ def gemm_trace_read():
     columns), av, bv (none | chan | im2col) with sh, sw, epi (none | plain |
     scatter | sscatter), bias (none | row | col), relu."""
     return _trace_records(_lib.caffe_gemm_trace_read)
+
+
+def gemm_trace_readers():
+    """(cursor, wide64): of the gemm calls traced since gemm_trace(True),
+    how many read their operands through the 32-bit staging cursors and how
+    many through the 64-bit reader."""
+    cur, wide = ctypes.c_long(0), ctypes.c_long(0)
+    _ck(_lib.caffe_gemm_trace_readers(ctypes.byref(cur), ctypes.byref(wide)))
+    return cur.value, wide.value
+
+
+def fastdiv_selftest(d_lo, d_hi):
+    """Mismatches of the GEMM staging's exact fast division against / and %
+    for every divisor in [d_lo, d_hi] (host code; see caffe_amd.h)."""
+    n = _lib.caffe_fastdiv_selftest(d_lo, d_hi)
+    if n < 0:
+        raise CaffeError(_lib.caffe_last_error().decode())
+    return n
 
 
 def _trace_records(read):

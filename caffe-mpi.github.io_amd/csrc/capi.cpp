@@ -497,6 +497,38 @@ int caffe_gemm_trace_read(char* buf, int cap) {
   API_CATCH
 }
 
+int caffe_gemm_trace_readers(long* cursor, long* wide64) {
+  API_TRY
+  gpu::gemm_trace_readers(cursor, wide64);
+  return 0;
+  API_CATCH
+}
+
+long caffe_fastdiv_selftest(unsigned d_lo, unsigned d_hi) {
+  API_TRY
+  CHECK_GT_(d_lo, 0u);
+  CHECK_LE_((long)d_hi, kFastDivLimit);
+  long bad = 0;
+#pragma omp parallel for reduction(+ : bad) schedule(dynamic, 16)
+  for (long dl = d_lo; dl <= (long)d_hi; ++dl) {
+    const unsigned d = (unsigned)dl;
+    const FastDiv f = fastdiv_make(d);
+    auto check = [&](long n) {
+      if (n < 0 || n >= kFastDivLimit) return;
+      const unsigned u = (unsigned)n, q = fastdiv(u, f);
+      bad += q != u / d || u - q * d != u % d;
+    };
+    for (long n = 0; n <= (1L << 20); ++n) check(n);
+    for (long n = kFastDivLimit - 4096; n < kFastDivLimit; ++n) check(n);
+    // the multiples of d next to the limit, and their neighbours
+    const long top = (kFastDivLimit - 1) / d;
+    for (long k = std::max(0L, top - 4096); k <= top + 1; ++k)
+      for (long e = -1; e <= 1; ++e) check(k * (long)d + e);
+  }
+  return bad;
+  API_CATCH
+}
+
 int caffe_kernel_trace(int enable) {
   API_TRY
   gpu::kernel_trace(enable != 0);

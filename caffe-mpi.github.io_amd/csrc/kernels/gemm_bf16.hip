@@ -43,7 +43,10 @@ constexpr int PSTR = 2 * ROWS + 2;  // bf16 per pair-row (+1 word pad)
 template <int ROWS>
 constexpr int OPSZ = (BK / 2) * PSTR<ROWS>;  // bf16 per operand image
 
-// ---- staging: fp32 read16 -> bf16 convert -> LDS scatter
+// ---- staging: fp32 read16 -> bf16 convert -> LDS scatter.  These kernels
+// keep the 64-bit reader read16() and the 64-bit epilogue division
+// (store_acc<SPLITK, true>), not the fp32 kernels' staging cursors: they sit
+// at 256 VGPRs and spill more with the cursors.
 // row-contiguous source (thread holds (r, k0..k0+15)): paired b32 writes
 template <int PS>
 __device__ __forceinline__ void write_rowk(bf16* img, int r, int k0,
@@ -244,7 +247,7 @@ __launch_bounds__(256, 2) __global__ void k_gemm_bf16(GemmArgs g) {
   auto store = [&](const f32x16& a, int ti, int tj) {
     const long col = n0 + wc * 64 + tj * 32 + row_in;
     if (col >= g.N) return;
-    store_acc<SPLITK>(g, a, m0 + wr * 64 + ti * 32, col, ksel);
+    store_acc<SPLITK, true>(g, a, m0 + wr * 64 + ti * 32, col, ksel);
   };
   store(acc00, 0, 0);
   store(acc01, 0, 1);
@@ -324,8 +327,8 @@ __launch_bounds__(512, 1) __global__ void k_gemm_bf16_wide(GemmArgs g) {
   for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
     for (int tj = 0; tj < 4; ++tj)
-      store_acc<SPLITK>(g, acc[ti][tj], m0 + wr * 64 + ti * 32,
-                        n0 + wc * 128 + tj * 32 + row_in, ksel);
+      store_acc<SPLITK, true>(g, acc[ti][tj], m0 + wr * 64 + ti * 32,
+                              n0 + wc * 128 + tj * 32 + row_in, ksel);
 }
 
 }  // namespace bf16gemm

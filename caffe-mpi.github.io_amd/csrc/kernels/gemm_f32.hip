@@ -40,16 +40,29 @@ void gemm_launch_bf16(hipStream_t s, bool transA, bool transB, dim3 grid,
 // are the M axis, B rows the N axis).  KCONTIG: the operand is stored
 // [row][K], contiguous along K (view axis allowed) — A when !TA, B when
 // TB; otherwise it is stored [K][row], contiguous along the row axis.
-template <bool KCONTIG>
-__device__ __forceinline__ void stage_load(const float* P, long r0, long k0,
-                                           long ld, long R, long K,
+// The thread's tile row (KCONTIG) or 16-row chunk is the half of its
+// staging address the K-loop never changes: tile_cursor() takes it apart
+// once, stage_load() reads a K-tile from the cursor and k0.
+template <bool KCONTIG, bool W64>
+__device__ __forceinline__ StageCur tile_cursor(long r0, long R,
+                                                const GemmView& v) {
+  const int t = threadIdx.x;
+  return make_cursor<KCONTIG, W64>(
+      r0 + (KCONTIG ? (t & 127) : (t >> 5) * 16), R, v);
+}
+template <bool KCONTIG, bool W64, bool PLAIN = false>
+__device__ __forceinline__ void stage_load(const float* P,
+                                           const StageCur& c, long r0,
+                                           long k0, long ld, long R, long K,
                                            const GemmView& v,
                                            float (&r)[16]) {
   const int t = threadIdx.x;
   if (KCONTIG)
-    read16(P, r0 + (t & 127), k0 + (t >> 7) * 16, ld, R, K, v, r);
+    read16v<true, W64, PLAIN>(P, c, r0 + (t & 127), k0 + (t >> 7) * 16, ld,
+                              R, K, v, r);
   else
-    read16(P, k0 + (t & 31), r0 + (t >> 5) * 16, ld, K, R, v, r);
+    read16v<false, W64, PLAIN>(P, c, k0 + (t & 31), r0 + (t >> 5) * 16, ld,
+                               K, R, v, r);
 }
 
 template <bool KCONTIG>
@@ -68,12 +81,14 @@ __device__ __forceinline__ void stage_write(float* S, const float (&r)[16]) {
   }
 }
 // both operands of a 128x128 block tile at K offset k0
-template <bool TA, bool TB>
-__device__ __forceinline__ void load_tile(const GemmArgs& g, long m0,
+template <bool TA, bool TB, bool W64>
+__device__ __forceinline__ void load_tile(const GemmArgs& g,
+                                          const StageCur& ca,
+                                          const StageCur& cb, long m0,
                                           long n0, long k0, float (&a)[16],
                                           float (&b)[16]) {
-  stage_load<!TA>(g.A, m0, k0, g.lda, g.M, g.K, g.av, a);
-  stage_load<TB>(g.B, n0, k0, g.ldb, g.N, g.K, g.bv, b);
+  stage_load<!TA, W64, TA>(g.A, ca, m0, k0, g.lda, g.M, g.K, g.av, a);
+  stage_load<TB, W64>(g.B, cb, n0, k0, g.ldb, g.N, g.K, g.bv, b);
 }
 template <bool TA, bool TB>
 __device__ __forceinline__ void write_tile(float* As, float* Bs,
@@ -83,7 +98,7 @@ __device__ __forceinline__ void write_tile(float* As, float* Bs,
   stage_write<TB>(Bs, b);
 }
 
-template <bool TA, bool TB, bool SPLITK>
+template <bool TA, bool TB, bool SPLITK, bool W64>
 __launch_bounds__(256, 2) __global__ void k_gemm_f32(GemmArgs g) {
   // one LDS arena carved into As[2] | Bs[2]; the K-waves combine below
   // reuses it after the K-loop
@@ -118,12 +133,16 @@ __launch_bounds__(256, 2) __global__ void k_gemm_f32(GemmArgs g) {
 
   f32x16 acc00 = {}, acc01 = {}, acc10 = {}, acc11 = {};
   float ra[16], rb[16];
+  // staging cursors: the K-invariant half of this thread's A / B addresses
+  // (a transposed A is never a view — gemm() checks — and has none)
+  const StageCur ca = tile_cursor<!TA, W64 || TA>(m0, g.M, g.av);
+  const StageCur cb = tile_cursor<TB, W64>(n0, g.N, g.bv);
 
   // The 2x2 MFMA step below stands twice on purpose, in the plain loop and
   // in the K-waves loop: with one definition (lambda or function) the
   // compiler schedules the plain K-loop differently and it runs 5-15%
   // slower ("GEMM helper forms").
-  load_tile<TA, TB>(g, m0, n0, k_lo, ra, rb);
+  load_tile<TA, TB, W64>(g, ca, cb, m0, n0, k_lo, ra, rb);
   write_tile<TA, TB>(As(0), Bs(0), ra, rb);
   __syncthreads();
 
@@ -131,7 +150,8 @@ __launch_bounds__(256, 2) __global__ void k_gemm_f32(GemmArgs g) {
     int cur = 0;
     for (long t = 0; t < ntiles; ++t) {
       if (t + 1 < ntiles)  // issue next tile's global loads early (T14)
-        load_tile<TA, TB>(g, m0, n0, k_lo + (t + 1) * BK, ra, rb);
+        load_tile<TA, TB, W64>(g, ca, cb, m0, n0, k_lo + (t + 1) * BK, ra,
+                               rb);
       {
         const float* Ab = As(cur);
         const float* Bb = Bs(cur);
@@ -172,17 +192,19 @@ __launch_bounds__(256, 2) __global__ void k_gemm_f32(GemmArgs g) {
     const int kk1 = (kwaves == 4) ? kk0 + BK / 2 : BK;
     // prologue already staged tile 0 into buf0; stage tile 1 into buf1
     if (1 < ntiles) {
-      load_tile<TA, TB>(g, m0, n0, k_lo + BK, ra, rb);
+      load_tile<TA, TB, W64>(g, ca, cb, m0, n0, k_lo + BK, ra, rb);
       write_tile<TA, TB>(As(1), Bs(1), ra, rb);
     }
     __syncthreads();
     for (long p = 0; p < ntiles; p += 2) {
       const long t_next0 = p + 2, t_next1 = p + 3;
       if (t_next0 < ntiles)
-        load_tile<TA, TB>(g, m0, n0, k_lo + t_next0 * BK, ra, rb);
+        load_tile<TA, TB, W64>(g, ca, cb, m0, n0, k_lo + t_next0 * BK, ra,
+                               rb);
       float ra2[16], rb2[16];
       if (t_next1 < ntiles)
-        load_tile<TA, TB>(g, m0, n0, k_lo + t_next1 * BK, ra2, rb2);
+        load_tile<TA, TB, W64>(g, ca, cb, m0, n0, k_lo + t_next1 * BK, ra2,
+                               rb2);
       if (p + grp < ntiles) {
         const float* Ab = As(grp);
         const float* Bb = Bs(grp);
@@ -214,10 +236,10 @@ __launch_bounds__(256, 2) __global__ void k_gemm_f32(GemmArgs g) {
     return;
 
   const long row0 = m0 + wr * 64, col0 = n0 + wc * 64 + row_in;
-  store_acc<SPLITK>(g, acc00, row0, col0, ksel);
-  store_acc<SPLITK>(g, acc01, row0, col0 + 32, ksel);
-  store_acc<SPLITK>(g, acc10, row0 + 32, col0, ksel);
-  store_acc<SPLITK>(g, acc11, row0 + 32, col0 + 32, ksel);
+  store_acc<SPLITK, W64>(g, acc00, row0, col0, ksel);
+  store_acc<SPLITK, W64>(g, acc01, row0, col0 + 32, ksel);
+  store_acc<SPLITK, W64>(g, acc10, row0 + 32, col0, ksel);
+  store_acc<SPLITK, W64>(g, acc11, row0 + 32, col0 + 32, ksel);
 }
 
 // ==================================================================
@@ -230,7 +252,7 @@ __launch_bounds__(256, 2) __global__ void k_gemm_f32(GemmArgs g) {
 // MFMA row is a real output row.  Structure otherwise mirrors k_gemm_f32
 // (register T14 pipeline, one barrier per K-tile, same epilogue/split-K
 // slabs); at TM=64 the LDS footprint (50 KB) admits 3 blocks/CU.
-template <bool TA, bool TB, int TM, bool SPLITK>
+template <bool TA, bool TB, int TM, bool SPLITK, bool W64>
 __launch_bounds__(256, TM == 64 ? 3 : 2) __global__
     void k_gemm_slim(GemmArgs g) {
   constexpr int TN = TM == 32 ? 256 : 128;
@@ -275,12 +297,22 @@ __launch_bounds__(256, TM == 64 ? 3 : 2) __global__
   const bool a_mine = TA ? a_m < TM : t < 2 * TM;
   const int b_n = TB ? (t & (TN - 1)) : (t >> 5) * (TN / 8);
   const int b_k = TB ? (TN == 256 ? 0 : (t >> 7) * 16) : (t & 31);
+  // staging cursors: the K-invariant half of the addresses above (A's
+  // row, B's column or column chunk(s); a transposed A is never a view —
+  // gemm() checks — and has none)
+  const StageCur ca = make_cursor<!TA, W64 || TA>(m0 + a_m, g.M, g.av);
+  const StageCur cb = make_cursor<TB, W64>(n0 + b_n, g.N, g.bv);
+  const StageCur cb2 = (!TB && TN == 256)
+                           ? make_cursor<false, W64>(n0 + b_n + 16, g.N, g.bv)
+                           : cb;
   auto a_load = [&](long k0) {
     if (!a_mine) return;
     if (!TA)
-      read16(g.A, m0 + a_m, k0 + a_k, g.lda, g.M, g.K, g.av, ra);
+      read16v<true, W64>(g.A, ca, m0 + a_m, k0 + a_k, g.lda, g.M, g.K, g.av,
+                         ra);
     else
-      read16(g.A, k0 + a_k, m0 + a_m, g.lda, g.K, g.M, g.av, ra);
+      read16v<false, W64, true>(g.A, ca, k0 + a_k, m0 + a_m, g.lda, g.K,
+                                g.M, g.av, ra);
   };
   auto a_write = [&](float* A_) {
     if (!a_mine) return;
@@ -294,13 +326,17 @@ __launch_bounds__(256, TM == 64 ? 3 : 2) __global__
   };
   auto b_load = [&](long k0) {
     if (!TB) {
-      read16(g.B, k0 + b_k, n0 + b_n, g.ldb, g.K, g.N, g.bv, rb);
+      read16v<false, W64>(g.B, cb, k0 + b_k, n0 + b_n, g.ldb, g.K, g.N,
+                          g.bv, rb);
       if (TN == 256)
-        read16(g.B, k0 + b_k, n0 + b_n + 16, g.ldb, g.K, g.N, g.bv, rb2);
+        read16v<false, W64>(g.B, cb2, k0 + b_k, n0 + b_n + 16, g.ldb, g.K,
+                            g.N, g.bv, rb2);
     } else {
-      read16(g.B, n0 + b_n, k0 + b_k, g.ldb, g.N, g.K, g.bv, rb);
+      read16v<true, W64>(g.B, cb, n0 + b_n, k0 + b_k, g.ldb, g.N, g.K, g.bv,
+                         rb);
       if (TN == 256)
-        read16(g.B, n0 + b_n, k0 + b_k + 16, g.ldb, g.N, g.K, g.bv, rb2);
+        read16v<true, W64>(g.B, cb, n0 + b_n, k0 + b_k + 16, g.ldb, g.N,
+                           g.K, g.bv, rb2);
     }
   };
   auto b_write = [&](float* B_) {
@@ -353,7 +389,7 @@ __launch_bounds__(256, TM == 64 ? 3 : 2) __global__
   auto store = [&](const f32x16& a, int tj) {
     const long col = n0 + wc * 64 + tj * 32 + row_in;
     if (col >= g.N) return;
-    store_acc<SPLITK>(g, a, m0 + wr * 32, col, ksel);
+    store_acc<SPLITK, W64>(g, a, m0 + wr * 32, col, ksel);
   };
   store(acc0, 0);
   store(acc1, 1);
@@ -501,6 +537,9 @@ constexpr size_t kTraceCap = 4096;
 static std::atomic<bool> g_trace_on{false};
 static std::mutex g_trace_mu;
 static std::vector<GemmRoute> g_trace_log;
+// traced calls by operand reader: [0] staging cursors, [1] 64-bit reader
+// (W64 fp32 kernels and every bf16 kernel)
+static std::atomic<long> g_reader_calls[2];
 
 static int view_kind(const GemmView* v) {  // 0 none, 1 chan, 2 im2col
   return !v || !v->spad ? 0 : (v->kh > 0 ? 2 : 1);
@@ -526,8 +565,15 @@ void gemm_trace(bool enable) {
   if (enable) {
     g_trace_log.clear();
     g_trace_log.reserve(kTraceCap);
+    g_reader_calls[0] = 0;
+    g_reader_calls[1] = 0;
   }
   g_trace_on.store(enable, std::memory_order_relaxed);
+}
+
+void gemm_trace_readers(long* cursor, long* wide64) {
+  *cursor = g_reader_calls[0].load();
+  *wide64 = g_reader_calls[1].load();
 }
 
 long gemm_trace_read(char* buf, long cap) {
@@ -552,6 +598,42 @@ long gemm_trace_read(char* buf, long cap) {
     len += n;
   }
   return len;
+}
+
+// ---- limits of the 32-bit staging (gemm_common.hpp).  Row, column and K
+// indices, a tile's overrun past the edge included, are fastdiv dividends
+// and stay below 2^31; a viewed operand is addressed by a 32-bit byte
+// offset from its base, so it holds at most 2^30 elements.
+// CAFFE_GEMM_W64=1 sends every call to the 64-bit kernels (A/B and tests).
+constexpr long kIdx32Max = kFastDivLimit - 4096;
+static bool index32_ok(long M, long N, long K, const GemmEpi* epi) {
+  static const bool force64 = [] {
+    const char* e = getenv("CAFFE_GEMM_W64");
+    return e && atoi(e) != 0;
+  }();
+  if (force64) return false;
+  if (M > kIdx32Max || N > kIdx32Max || K > kIdx32Max) return false;
+  return !(epi && epi->spad > 0 && epi->spad >= kFastDivLimit);
+}
+// fills the view's reciprocals and strides; false when it does not fit.
+// axis: length of the GEMM axis the view's images lie along.
+static bool fill_view32(GemmView& v, long axis) {
+  if (!v.spad) return true;
+  const long per_chan = v.kh > 0 ? (long)v.H * v.W : v.S;
+  const long per_img = v.chan * per_chan;
+  const long nimg = (axis + v.spad - 1) / v.spad;
+  if (v.spad >= kFastDivLimit || nimg * per_img > (1L << 30)) return false;
+  v.fd_spad = fastdiv_make((unsigned long)v.spad);
+  v.img = (unsigned)per_img;
+  v.hw = (unsigned)per_chan;
+  if (v.kh > 0) {
+    CHECK_GT_(v.kw, 0);
+    CHECK_GT_(v.OW, 0);
+    v.fd_ow = fastdiv_make((unsigned long)v.OW);
+    v.fd_khkw = fastdiv_make((unsigned long)v.kh * v.kw);
+    v.fd_kw = fastdiv_make((unsigned long)v.kw);
+  }
+  return true;
 }
 
 void gemm(hipStream_t s, bool transA, bool transB, long M, long N, long K,
@@ -590,12 +672,30 @@ void gemm(hipStream_t s, bool transA, bool transB, long M, long N, long K,
   }
   if (aview) g.av = *aview;
   if (bview) g.bv = *bview;
+  // 32-bit staging (the cursor kernels): for calls whose B is a view, when
+  // every index the kernels decompose and every viewed operand's byte
+  // offset fit.  Every other call goes to the W64 kernels, which are the
+  // 64-bit reader and epilogue division unchanged: sizes past the limits,
+  // and calls with a plain B (IP layers, explicit-col convs — wgrad with a
+  // dY view as A included), whose plain path measured 6-10 % slower next to
+  // the cursor code.  A's image axis is K (views need
+  // !transA), B's is K when transposed, N otherwise.
+  bool w64 = !bview || !index32_ok(M, N, K, epi);
+  if (!w64 && aview && !fill_view32(g.av, K)) w64 = true;
+  if (!w64 && !fill_view32(g.bv, transB ? K : N)) w64 = true;
+  if (!w64 && epi && epi->spad > 0) {
+    g.fd_spad = fastdiv_make((unsigned long)epi->spad);
+    if (epi->OWo > 0) g.fd_owo = fastdiv_make((unsigned long)epi->OWo);
+  }
   const GemmRoute r = pick_route(M, N, K, transA, transB, epi != nullptr,
                                  beta, Engine::get().gemm_bf16);
   g.tn = r.tn;
   g.tiles = r.tm * r.tn;
-  if (g_trace_on.load(std::memory_order_relaxed))
+  const bool bf16_fam = r.fam == kBf16_128 || r.fam == kBf16Wide;
+  if (g_trace_on.load(std::memory_order_relaxed)) {
     trace_route(r, epi, aview, bview);
+    g_reader_calls[w64 || bf16_fam].fetch_add(1, std::memory_order_relaxed);
+  }
 
   // ("gemm_tt" has no kernel any more; the class stays registered so perf
   // reports keep their four gemm lines)
@@ -624,7 +724,7 @@ void gemm(hipStream_t s, bool transA, bool transB, long M, long N, long K,
     g.SK = r.sk;
   }
   const dim3 grid((unsigned)g.tiles, 1, (unsigned)r.sk);
-  if (r.fam == kBf16_128 || r.fam == kBf16Wide) {
+  if (bf16_fam) {
     gemm_launch_bf16(s, transA, transB, grid, g, r.sk > 1,
                      r.fam == kBf16Wide);
   } else {
@@ -632,15 +732,22 @@ void gemm(hipStream_t s, bool transA, bool transB, long M, long N, long K,
         transA, transB, r.sk > 1, [&](auto ta, auto tb, auto sk) {
           constexpr bool TA = decltype(ta)::value, TB = decltype(tb)::value,
                          SPLITK = decltype(sk)::value;
-          if (r.fam == kSlim32)
-            hipLaunchKernelGGL((k_gemm_slim<TA, TB, 32, SPLITK>), grid,
-                               dim3(256), 0, s, g);
-          else if (r.fam == kSlim64)
-            hipLaunchKernelGGL((k_gemm_slim<TA, TB, 64, SPLITK>), grid,
-                               dim3(256), 0, s, g);
+          auto launch = [&](auto wide) {
+            constexpr bool W64 = decltype(wide)::value;
+            if (r.fam == kSlim32)
+              hipLaunchKernelGGL((k_gemm_slim<TA, TB, 32, SPLITK, W64>),
+                                 grid, dim3(256), 0, s, g);
+            else if (r.fam == kSlim64)
+              hipLaunchKernelGGL((k_gemm_slim<TA, TB, 64, SPLITK, W64>),
+                                 grid, dim3(256), 0, s, g);
+            else
+              hipLaunchKernelGGL((k_gemm_f32<TA, TB, SPLITK, W64>), grid,
+                                 dim3(256), 0, s, g);
+          };
+          if (w64)
+            launch(std::true_type{});
           else
-            hipLaunchKernelGGL((k_gemm_f32<TA, TB, SPLITK>), grid,
-                               dim3(256), 0, s, g);
+            launch(std::false_type{});
         });
   }
   if (r.sk > 1) launch_splitk_reduce(s, g.slab, M * N, r.sk, C);

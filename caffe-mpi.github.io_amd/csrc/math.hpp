@@ -94,6 +94,28 @@ CAMD_HD inline float solver_rule_step(float g, float w, float& h, float& h2,
   }
 }
 
+// --------------------------------------------------------- exact fast division
+// n / d for 0 <= n < 2^31 and 1 <= d <= 2^31 as multiply-high, add and shift
+// (Granlund & Montgomery's round-up form: with l = ceil(log2 d) and
+// M = ceil(2^(32+l) / d) in [2^32, 2^33), n / d == (n * M) >> (32 + l)
+// whenever n * (M*d - 2^(32+l)) < 2^(32+l), which n < 2^31 guarantees; mul
+// holds M - 2^32, and mulhi(n, mul) + n cannot overflow below 2^31).  The
+// magic is computed on the host; the default divides by 1.  The GEMM
+// staging and epilogue decompose their view indices with it.
+constexpr long kFastDivLimit = 1L << 31;  // dividends and divisors
+struct FastDiv {
+  unsigned mul = 0, sh = 0;
+};
+inline FastDiv fastdiv_make(unsigned long d) {
+  FastDiv f;
+  while ((1ul << f.sh) < d) ++f.sh;
+  f.mul = (unsigned)((((1ul << (32 + f.sh)) + d - 1) / d) - (1ul << 32));
+  return f;
+}
+CAMD_HD inline unsigned fastdiv(unsigned n, FastDiv f) {
+  return ((unsigned)(((unsigned long long)n * f.mul) >> 32) + n) >> f.sh;
+}
+
 // ------------------------------------------------------------ GPU launchers
 namespace gpu {
 
@@ -136,6 +158,12 @@ struct GemmView {
   int H = 0, W = 0, OW = 0;            // input dims / output row width
   int sh = 1, sw = 1;  // conv strides (round 2: strided implicit im2col —
                        // conv1 7x7s2, the 1x1s2 projections, AlexNet s4)
+  // 32-bit staging (filled by gemm(), never by the caller): magics of the
+  // divisors the staging decomposes by, and the per-image / per-channel
+  // element strides it would otherwise multiply out per element
+  FastDiv fd_spad, fd_ow, fd_khkw, fd_kw;
+  unsigned img = 0;  // elements per image: chan * (kh > 0 ? H*W : S)
+  unsigned hw = 0;   // elements per channel: kh > 0 ? H*W : S
 };
 
 // Wt[ci][co*kh*kw + ki*kw + kj] = W[co][ci][kh-1-ki][kw-1-kj] per group —
@@ -156,6 +184,10 @@ void gemm(hipStream_t s, bool transA, bool transB, long M, long N, long K,
 // cap > 0) and returns the length of the full text.
 void gemm_trace(bool enable);
 long gemm_trace_read(char* buf, long cap);
+// Of the calls traced since the last enable: how many read their operands
+// through the 32-bit staging cursors, and how many through the 64-bit
+// reader (the W64 fp32 kernels and every bf16 kernel).
+void gemm_trace_readers(long* cursor, long* wide64);
 
 // Variant trace of the elementwise launch wrappers (pooling, BN statistics,
 // LRN, softmax, segmented SGD): which specialised kernel a call launched and

@@ -175,6 +175,11 @@ int caffe_perf_reset(void);
  * a first call of cap 0. */
 int caffe_gemm_trace(int enable);
 int caffe_gemm_trace_read(char* buf, int cap);
+/* Of the calls traced since the trace was last enabled: how many read their
+ * operands through the 32-bit staging cursors (*cursor) and how many through
+ * the 64-bit reader (*wide64: calls with a plain B, sizes past the 32-bit
+ * limits, CAFFE_GEMM_W64=1, and every bf16 kernel). */
+int caffe_gemm_trace_readers(long* cursor, long* wide64);
 /* Kernel variant trace (off by default), same contract as the GEMM route
  * trace: while enabled, the pooling, BatchNorm-statistics, LRN, softmax and
  * segmented-SGD launch wrappers record one line per call, e.g.
@@ -185,6 +190,13 @@ int caffe_gemm_trace_read(char* buf, int cap);
  * "op=solver_seg rule=adam reg=L2 lo=0 hi=272 nseg=6". */
 int caffe_kernel_trace(int enable);
 int caffe_kernel_trace_read(char* buf, int cap);
+/* Self-test of the exact fast division the GEMM staging decomposes its view
+ * indices with (host code, no GPU): for every divisor in [d_lo, d_hi]
+ * compares quotient and remainder with / and % over the dividends 0..2^20,
+ * the 4096 values below the 2^31 dividend limit and the last 4096 multiples
+ * of the divisor below that limit, each +-1.  Returns the number of
+ * mismatches (0 = exact), -1 on a bad range. */
+long caffe_fastdiv_selftest(unsigned d_lo, unsigned d_hi);
 
 #ifdef __cplusplus
 }
