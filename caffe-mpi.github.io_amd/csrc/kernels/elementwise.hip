@@ -60,19 +60,6 @@ static inline void ktrace(int op, int var = kVarNone, long a = 0, long b = 0,
   if (g_ktrace_on.load(std::memory_order_relaxed))
     ktrace_push(op, var, a, b, c);
 }
-// BN stats: the largest per-block span (n1 - n0) * per over the nb batch
-// slices, with the slice bounds of k_bn_*_stats*; computed only when tracing
-static inline void ktrace_bn(int op, int var, int N, int nb, long per) {
-  if (!g_ktrace_on.load(std::memory_order_relaxed)) return;
-  long span_max = 0;
-  for (int slice = 0; slice < nb; ++slice) {
-    const int n0 = (int)((long)N * slice / nb);
-    const int n1 = (int)((long)N * (slice + 1) / nb);
-    span_max = std::max(span_max, (n1 - n0) * per);
-  }
-  ktrace_push(op, var, nb, span_max, 0);
-}
-
 void kernel_trace(bool enable) {
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   if (enable) {
@@ -307,17 +294,40 @@ void axpy(hipStream_t s, long n, float a, const float* x, float* y) {
 }
 
 // ------------------------------------------------------------ pooling
+// flat index over [nc][H][W] -> (w, h, nc): the output pixel of the forward
+// kernels (called with OW, OH), the input pixel of the backward ones
+struct PoolIdx {
+  int w, h;
+  long nc;
+};
+__device__ __forceinline__ PoolIdx pool_idx(long idx, int W, int H) {
+  return {(int)(idx % W), (int)((idx / W) % H), idx / ((long)W * H)};
+}
+// [p0, p1): the output positions, of O along one axis, whose k-wide window
+// at stride s covers padded input coordinate t = h + pad >= 0.  With the
+// stride a template constant S > 0 the divisions are unsigned (t - k >= 0
+// where it is divided) and fold away: nothing at S = 1, shifts at S = 2.
+struct WinRange {
+  int p0, p1;
+};
+template <int S = 0>
+__device__ __forceinline__ WinRange pool_win_range(int t, int k, int s,
+                                                   int O) {
+  if constexpr (S > 0)
+    return {t < k ? 0 : (int)((unsigned)(t - k) / S) + 1,
+            min((int)((unsigned)t / S) + 1, O)};
+  return {t < k ? 0 : (t - k) / s + 1, min(t / s + 1, O)};
+}
+
 __global__ void k_pool_max_fwd(const float* __restrict__ x, int N, int C,
                                int H, int W, int kh, int kw, int ph, int pw,
                                int sh, int sw, int OH, int OW,
                                float* __restrict__ y, int* __restrict__ mask) {
   const long total = (long)N * C * OH * OW;
   GRID_STRIDE(idx, total) {
-    const int ow = (int)(idx % OW);
-    const int oh = (int)((idx / OW) % OH);
-    const long nc = idx / ((long)OW * OH);
-    const float* xp = x + nc * H * W;
-    int hs = oh * sh - ph, ws = ow * sw - pw;
+    const PoolIdx o = pool_idx(idx, OW, OH);
+    const float* xp = x + o.nc * H * W;
+    int hs = o.h * sh - ph, ws = o.w * sw - pw;
     const int he = min(hs + kh, H), we = min(ws + kw, W);
     hs = max(hs, 0);
     ws = max(ws, 0);
@@ -346,11 +356,9 @@ __global__ void k_pool_max_fwd3(const float* __restrict__ x, int N, int C,
                                 int* __restrict__ mask) {
   const long total = (long)N * C * OH * OW;
   GRID_STRIDE(idx, total) {
-    const int ow = (int)(idx % OW);
-    const int oh = (int)((idx / OW) % OH);
-    const long nc = idx / ((long)OW * OH);
-    const float* xp = x + nc * H * W;
-    const int hs = oh * sh - ph, ws = ow * sw - pw;
+    const PoolIdx o = pool_idx(idx, OW, OH);
+    const float* xp = x + o.nc * H * W;
+    const int hs = o.h * sh - ph, ws = o.w * sw - pw;
     float v[9];
 #pragma unroll
     for (int a = 0; a < 3; ++a)
@@ -405,19 +413,15 @@ __global__ void k_pool_max_bwd(const float* __restrict__ dy,
                                float* __restrict__ dx) {
   const long total = (long)N * C * H * W;
   GRID_STRIDE(idx, total) {
-    const int w = (int)(idx % W);
-    const int h = (int)((idx / W) % H);
-    const long nc = idx / ((long)W * H);
-    const int me = h * W + w;
-    const int ph0 = (h + ph < kh) ? 0 : (h + ph - kh) / sh + 1;
-    const int ph1 = min((h + ph) / sh + 1, OH);
-    const int pw0 = (w + pw < kw) ? 0 : (w + pw - kw) / sw + 1;
-    const int pw1 = min((w + pw) / sw + 1, OW);
+    const PoolIdx p = pool_idx(idx, W, H);
+    const int me = p.h * W + p.w;
+    const WinRange ra = pool_win_range(p.h + ph, kh, sh, OH);
+    const WinRange rb = pool_win_range(p.w + pw, kw, sw, OW);
     float acc = 0.f;
-    const float* dyp = dy + nc * OH * OW;
-    const int* mp = mask + nc * OH * OW;
-    for (int a = ph0; a < ph1; ++a)
-      for (int b = pw0; b < pw1; ++b)
+    const float* dyp = dy + p.nc * OH * OW;
+    const int* mp = mask + p.nc * OH * OW;
+    for (int a = ra.p0; a < ra.p1; ++a)
+      for (int b = rb.p0; b < rb.p1; ++b)
         if (mp[a * OW + b] == me) acc += dyp[a * OW + b];
     dx[idx] = acc;
   }
@@ -426,120 +430,43 @@ __global__ void k_pool_max_bwd(const float* __restrict__ dy,
 // candidate windows — unroll them with predicates so all 18 mask/dy
 // loads issue before any wait (the generic loop was latency-serialized,
 // 78% parked).  Ascending (a, b) — fixed, deterministic order.
+// S = 0 takes the strides at run time.  S = 1 (the 13 GoogLeNet inception
+// pools) and S = 2 (the ResNet/GoogLeNet/AlexNet downsampling pools) are
+// the stride at compile time: the window bounds lose their divisions (the
+// run-time form pays four), and at stride 2 an input pixel overlaps at
+// most 2x2 windows, so the gather is 4 dy + 4 mask loads instead of 9 + 9.
+template <int S>
 __global__ void k_pool_max_bwd3(const float* __restrict__ dy,
                                 const int* __restrict__ mask, int N, int C,
                                 int H, int W, int ph, int pw, int sh,
                                 int sw, int OH, int OW,
                                 float* __restrict__ dx) {
+  constexpr int NW = S == 2 ? 2 : 3;  // candidate windows per axis
   const long total = (long)N * C * H * W;
   GRID_STRIDE(idx, total) {
-    const int w = (int)(idx % W);
-    const int h = (int)((idx / W) % H);
-    const long nc = idx / ((long)W * H);
-    const int me = h * W + w;
-    const int ph0 = (h + ph < 3) ? 0 : (h + ph - 3) / sh + 1;
-    const int ph1 = min((h + ph) / sh + 1, OH);
-    const int pw0 = (w + pw < 3) ? 0 : (w + pw - 3) / sw + 1;
-    const int pw1 = min((w + pw) / sw + 1, OW);
-    const float* dyp = dy + nc * OH * OW;
-    const int* mp = mask + nc * OH * OW;
-    bool hit[9];
-    float d[9];
+    const PoolIdx p = pool_idx(idx, W, H);
+    const int me = p.h * W + p.w;
+    const WinRange ra = pool_win_range<S>(p.h + ph, 3, sh, OH);
+    const WinRange rb = pool_win_range<S>(p.w + pw, 3, sw, OW);
+    const float* dyp = dy + p.nc * OH * OW;
+    const int* mp = mask + p.nc * OH * OW;
+    bool hit[NW * NW];
+    float d[NW * NW];
 #pragma unroll
-    for (int da = 0; da < 3; ++da)
+    for (int da = 0; da < NW; ++da)
 #pragma unroll
-      for (int db = 0; db < 3; ++db) {
-        const int a = ph0 + da, b = pw0 + db;
-        const bool ok = a < ph1 && b < pw1;
+      for (int db = 0; db < NW; ++db) {
+        const int a = ra.p0 + da, b = rb.p0 + db;
+        const bool ok = a < ra.p1 && b < rb.p1;
         const int off = ok ? a * OW + b : 0;
-        hit[da * 3 + db] = ok && mp[off] == me;
-        d[da * 3 + db] = dyp[off];
+        hit[da * NW + db] = ok && mp[off] == me;
+        d[da * NW + db] = dyp[off];
       }
     float acc = 0.f;
 #pragma unroll
-    for (int i = 0; i < 9; ++i)
+    for (int i = 0; i < NW * NW; ++i)
       if (hit[i]) acc += d[i];  // select, not multiply: a stray NaN in a
                                 // NON-matching window must not leak in
-    dx[idx] = acc;
-  }
-}
-
-// 3x3 STRIDE-2 form (the ResNet/GoogLeNet/AlexNet downsampling pools):
-// at stride 2 an input pixel overlaps at most 2x2 output windows, so the
-// gather loop is 2x2 — 4 dy + 4 mask loads instead of the generic form's
-// 9+9 — and the stride divisions become shifts
-__global__ void k_pool_max_bwd3s2(const float* __restrict__ dy,
-                                  const int* __restrict__ mask, int N,
-                                  int C, int H, int W, int ph, int pw,
-                                  int OH, int OW, float* __restrict__ dx) {
-  const long total = (long)N * C * H * W;
-  GRID_STRIDE(idx, total) {
-    const int w = (int)(idx % W);
-    const int h = (int)((idx / W) % H);
-    const long nc = idx / ((long)W * H);
-    const int me = h * W + w;
-    const int th = h + ph, tw = w + pw;  // >= 0
-    const int ph0 = (th < 3) ? 0 : ((th - 3) >> 1) + 1;
-    const int ph1 = min((th >> 1) + 1, OH);
-    const int pw0 = (tw < 3) ? 0 : ((tw - 3) >> 1) + 1;
-    const int pw1 = min((tw >> 1) + 1, OW);
-    const float* dyp = dy + nc * OH * OW;
-    const int* mp = mask + nc * OH * OW;
-    bool hit[4];
-    float d[4];
-#pragma unroll
-    for (int da = 0; da < 2; ++da)
-#pragma unroll
-      for (int db = 0; db < 2; ++db) {
-        const int a = ph0 + da, b = pw0 + db;
-        const bool ok = a < ph1 && b < pw1;
-        const int off = ok ? a * OW + b : 0;
-        hit[da * 2 + db] = ok && mp[off] == me;
-        d[da * 2 + db] = dyp[off];
-      }
-    float acc = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (hit[i]) acc += d[i];  // select, not multiply (NaN containment)
-    dx[idx] = acc;
-  }
-}
-
-// 3x3 STRIDE-1 form (the 13 GoogLeNet inception pools): window bounds
-// become max/min — no per-element divisions at all beyond the index
-// decompose (the generic form pays five)
-__global__ void k_pool_max_bwd3s1(const float* __restrict__ dy,
-                                  const int* __restrict__ mask, int N,
-                                  int C, int H, int W, int ph, int pw,
-                                  int OH, int OW, float* __restrict__ dx) {
-  const long total = (long)N * C * H * W;
-  GRID_STRIDE(idx, total) {
-    const int w = (int)(idx % W);
-    const int h = (int)((idx / W) % H);
-    const long nc = idx / ((long)W * H);
-    const int me = h * W + w;
-    const int ph0 = max(h + ph - 2, 0);
-    const int ph1 = min(h + ph + 1, OH);
-    const int pw0 = max(w + pw - 2, 0);
-    const int pw1 = min(w + pw + 1, OW);
-    const float* dyp = dy + nc * OH * OW;
-    const int* mp = mask + nc * OH * OW;
-    bool hit[9];
-    float d[9];
-#pragma unroll
-    for (int da = 0; da < 3; ++da)
-#pragma unroll
-      for (int db = 0; db < 3; ++db) {
-        const int a = ph0 + da, b = pw0 + db;
-        const bool ok = a < ph1 && b < pw1;
-        const int off = ok ? a * OW + b : 0;
-        hit[da * 3 + db] = ok && mp[off] == me;
-        d[da * 3 + db] = dyp[off];
-      }
-    float acc = 0.f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i)
-      if (hit[i]) acc += d[i];
     dx[idx] = acc;
   }
 }
@@ -549,30 +476,27 @@ void pool_max_bwd(hipStream_t s, const float* dy, const int* mask, int N,
                   int sh, int sw, int OH, int OW, float* dx) {
   const long total = (long)N * C * H * W;
   PerfScope perf(PERF_CLASS("pool"), s, 0, 12.0 * total);
+  const dim3 grid(nblocks(total, 2)), block(TPB);
   if (kh == 3 && kw == 3 && sh == 1 && sw == 1) {
-    hipLaunchKernelGGL(k_pool_max_bwd3s1, dim3(nblocks(total, 2)),
-                       dim3(TPB), 0, s, dy, mask, N, C, H, W, ph, pw, OH,
-                       OW, dx);
+    hipLaunchKernelGGL(k_pool_max_bwd3<1>, grid, block, 0, s, dy, mask, N, C,
+                       H, W, ph, pw, sh, sw, OH, OW, dx);
     ktrace(kPoolMaxBwd, kVarK3S1);
     return;
   }
   if (kh == 3 && kw == 3 && sh == 2 && sw == 2) {
-    hipLaunchKernelGGL(k_pool_max_bwd3s2, dim3(nblocks(total, 2)),
-                       dim3(TPB), 0, s, dy, mask, N, C, H, W, ph, pw, OH,
-                       OW, dx);
+    hipLaunchKernelGGL(k_pool_max_bwd3<2>, grid, block, 0, s, dy, mask, N, C,
+                       H, W, ph, pw, sh, sw, OH, OW, dx);
     ktrace(kPoolMaxBwd, kVarK3S2);
     return;
   }
   if (kh == 3 && kw == 3) {
-    hipLaunchKernelGGL(k_pool_max_bwd3, dim3(nblocks(total, 2)), dim3(TPB),
-                       0, s, dy, mask, N, C, H, W, ph, pw, sh, sw, OH, OW,
-                       dx);
+    hipLaunchKernelGGL(k_pool_max_bwd3<0>, grid, block, 0, s, dy, mask, N, C,
+                       H, W, ph, pw, sh, sw, OH, OW, dx);
     ktrace(kPoolMaxBwd, kVarK3);
     return;
   }
-  hipLaunchKernelGGL(k_pool_max_bwd, dim3(nblocks(total, 2)), dim3(TPB), 0,
-                     s, dy, mask, N, C, H, W, kh, kw, ph, pw, sh, sw, OH,
-                     OW, dx);
+  hipLaunchKernelGGL(k_pool_max_bwd, grid, block, 0, s, dy, mask, N, C, H, W,
+                     kh, kw, ph, pw, sh, sw, OH, OW, dx);
   ktrace(kPoolMaxBwd, kVarGeneric);
 }
 
@@ -582,11 +506,9 @@ __global__ void k_pool_ave_fwd(const float* __restrict__ x, int N, int C,
                                float* __restrict__ y) {
   const long total = (long)N * C * OH * OW;
   GRID_STRIDE(idx, total) {
-    const int ow = (int)(idx % OW);
-    const int oh = (int)((idx / OW) % OH);
-    const long nc = idx / ((long)OW * OH);
-    const float* xp = x + nc * H * W;
-    int hs = oh * sh - ph, ws = ow * sw - pw;
+    const PoolIdx o = pool_idx(idx, OW, OH);
+    const float* xp = x + o.nc * H * W;
+    int hs = o.h * sh - ph, ws = o.w * sw - pw;
     int he = min(hs + kh, H + ph), we = min(ws + kw, W + pw);
     const int ps = (he - hs) * (we - ws);  // padded size (:201)
     hs = max(hs, 0);
@@ -615,17 +537,13 @@ __global__ void k_pool_ave_bwd(const float* __restrict__ dy, int N, int C,
                                float* __restrict__ dx) {
   const long total = (long)N * C * H * W;
   GRID_STRIDE(idx, total) {
-    const int w = (int)(idx % W);
-    const int h = (int)((idx / W) % H);
-    const long nc = idx / ((long)W * H);
-    const int ph0 = (h + ph < kh) ? 0 : (h + ph - kh) / sh + 1;
-    const int ph1 = min((h + ph) / sh + 1, OH);
-    const int pw0 = (w + pw < kw) ? 0 : (w + pw - kw) / sw + 1;
-    const int pw1 = min((w + pw) / sw + 1, OW);
+    const PoolIdx p = pool_idx(idx, W, H);
+    const WinRange ra = pool_win_range(p.h + ph, kh, sh, OH);
+    const WinRange rb = pool_win_range(p.w + pw, kw, sw, OW);
     float acc = 0.f;
-    const float* dyp = dy + nc * OH * OW;
-    for (int a = ph0; a < ph1; ++a)
-      for (int b = pw0; b < pw1; ++b) {
+    const float* dyp = dy + p.nc * OH * OW;
+    for (int a = ra.p0; a < ra.p1; ++a)
+      for (int b = rb.p0; b < rb.p1; ++b) {
         int hs = a * sh - ph, ws = b * sw - pw;
         const int he = min(hs + kh, H + ph), we = min(ws + kw, W + pw);
         const int ps = (he - hs) * (we - ws);
@@ -671,37 +589,45 @@ int bn_blocks_per_channel(int N, int C) {
   return std::max(1, std::min(N, 2048 / std::max(1, C)));
 }
 
-__global__ void k_bn_fwd_stats(const float* __restrict__ x, int N, int C,
-                               long S, int nb, double2* __restrict__ out) {
-  const int c = blockIdx.x % C;
-  const int slice = blockIdx.x / C;
-  const int n0 = (int)((long)N * slice / nb);
-  const int n1 = (int)((long)N * (slice + 1) / nb);
-  const int Si = (int)S;
-  const int span = (n1 - n0) * Si;
-  const int B = blockDim.x;
-  auto addr = [&](int i) {
-    const int n = n0 + i / Si;
-    const int sp = i - (n - n0) * Si;
-    return ((long)n * C + c) * S + sp;
-  };
-  double s1 = 0, s2 = 0, t1 = 0, t2 = 0;
-  int i = threadIdx.x;
-  for (; i + 3 * B < span; i += 4 * B) {  // 4 loads in flight (MLP)
-    const float v0 = x[addr(i)], v1 = x[addr(i + B)];
-    const float v2 = x[addr(i + 2 * B)], v3 = x[addr(i + 3 * B)];
-    s1 += (double)v0 + v1;
-    s2 += (double)v0 * v0 + (double)v1 * v1;
-    t1 += (double)v2 + v3;
-    t2 += (double)v2 * v2 + (double)v3 * v3;
+// Batch slice `slice` of nb covers the images [n0, n1).  The kernels and
+// the trace both take the bounds from here.
+struct BnSlice {
+  int n0, n1;
+};
+__host__ __device__ inline BnSlice bn_slice(int N, int slice, int nb) {
+  return {(int)((long)N * slice / nb), (int)((long)N * (slice + 1) / nb)};
+}
+// trace record of a statistics launch: the largest per-block span
+// (n1 - n0) * per over the nb batch slices; computed only when tracing
+static inline void ktrace_bn(int op, int var, int N, int nb, long per) {
+  if (!g_ktrace_on.load(std::memory_order_relaxed)) return;
+  long span_max = 0;
+  for (int slice = 0; slice < nb; ++slice) {
+    const BnSlice sl = bn_slice(N, slice, nb);
+    span_max = std::max(span_max, (sl.n1 - sl.n0) * per);
   }
-  for (; i < span; i += B) {
-    const double v = x[addr(i)];
-    s1 += v;
-    s2 += v * v;
+  ktrace_push(op, var, nb, span_max, 0);
+}
+// What one block of a statistics kernel reduces: channel c = blockIdx % C
+// over batch slice blockIdx / C — `span` loads, `per` of them per image
+// (S floats, or S / 4 float4 packs), the i-th at addr(i).
+struct BnBlock {
+  int c, slice, n0, span, per, C;
+  __device__ __forceinline__ long addr(int i) const {
+    const int n = n0 + i / per;
+    return ((long)n * C + c) * per + (i - (n - n0) * per);
   }
-  s1 += t1;
-  s2 += t2;
+};
+__device__ __forceinline__ BnBlock bn_block(int N, int C, int per, int nb) {
+  const int c = blockIdx.x % C, slice = blockIdx.x / C;
+  const BnSlice sl = bn_slice(N, slice, nb);
+  return {c, slice, sl.n0, (sl.n1 - sl.n0) * per, per, C};
+}
+// in-block tree reduce of the threads' (s1, s2) and the store of the
+// block's partial: fixed order, so the partials are deterministic
+__device__ __forceinline__ void bn_reduce_store(double s1, double s2,
+                                                const BnBlock& b, int nb,
+                                                double2* __restrict__ out) {
   __shared__ double sh1[TPB], sh2[TPB];
   sh1[threadIdx.x] = s1;
   sh2[threadIdx.x] = s2;
@@ -713,80 +639,68 @@ __global__ void k_bn_fwd_stats(const float* __restrict__ x, int N, int C,
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) out[(long)c * nb + slice] = {sh1[0], sh2[0]};
+  if (threadIdx.x == 0) out[(long)b.c * nb + b.slice] = {sh1[0], sh2[0]};
 }
+// a load of the statistics kernels is V = float, or f4 when S % 4 == 0
+template <typename V>
+constexpr int kLanes = sizeof(V) / sizeof(float);
+__device__ __forceinline__ float lane(float v, int) { return v; }
+__device__ __forceinline__ float lane(f4 v, int j) { return v[j]; }
 
-// f4 variant (S % 4 == 0: every ResNet spatial stage except 7x7=49):
-// quarters the load count and the per-element index divisions.  4-way
-// unrolled with independent partial sums: the rolled loop kept ONE load
-// in flight per wave (the accumulate chained on it), measuring 2.85 TB/s
-// with waves 59-81% parked — four independent loads per iteration is the
+// V = f4 (S % 4 == 0: every ResNet spatial stage except 7x7=49) quarters
+// the load count and the per-element index divisions.  4-way unrolled with
+// independent partial sums: the rolled loop kept ONE load in flight per
+// wave (the accumulate chained on it), measuring 2.85 TB/s with waves
+// 59-81% parked — four independent loads per iteration is the
 // memory-level-parallelism fix, not more occupancy.
-__global__ void k_bn_fwd_stats_v4(const f4* __restrict__ x4, int N, int C,
-                                  int S4, int nb, double2* __restrict__ out) {
-  const int c = blockIdx.x % C;
-  const int slice = blockIdx.x / C;
-  const int n0 = (int)((long)N * slice / nb);
-  const int n1 = (int)((long)N * (slice + 1) / nb);
-  const int span = (n1 - n0) * S4;
+template <typename V>
+__global__ void k_bn_fwd_stats(const V* __restrict__ x, int N, int C, int per,
+                               int nb, double2* __restrict__ out) {
+  constexpr int L = kLanes<V>;
+  const BnBlock b = bn_block(N, C, per, nb);
   const int B = blockDim.x;
   double s1 = 0, s2 = 0;
   double t1 = 0, t2 = 0;  // second accumulator pair halves the add chain
-  auto addr = [&](int i) {
-    const int n = n0 + i / S4;
-    const int sp = i - (n - n0) * S4;
-    return ((long)n * C + c) * S4 + sp;
-  };
   int i = threadIdx.x;
-  for (; i + 3 * B < span; i += 4 * B) {
-    const f4 v0 = x4[addr(i)];
-    const f4 v1 = x4[addr(i + B)];
-    const f4 v2 = x4[addr(i + 2 * B)];
-    const f4 v3 = x4[addr(i + 3 * B)];
+  for (; i + 3 * B < b.span; i += 4 * B) {  // 4 loads in flight (MLP)
+    const V v0 = x[b.addr(i)];
+    const V v1 = x[b.addr(i + B)];
+    const V v2 = x[b.addr(i + 2 * B)];
+    const V v3 = x[b.addr(i + 3 * B)];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s1 += (double)v0[j] + v1[j];
-      s2 += (double)v0[j] * v0[j] + (double)v1[j] * v1[j];
-      t1 += (double)v2[j] + v3[j];
-      t2 += (double)v2[j] * v2[j] + (double)v3[j] * v3[j];
+    for (int j = 0; j < L; ++j) {
+      const float a0 = lane(v0, j), a1 = lane(v1, j);
+      const float a2 = lane(v2, j), a3 = lane(v3, j);
+      s1 += (double)a0 + a1;
+      s2 += (double)a0 * a0 + (double)a1 * a1;
+      t1 += (double)a2 + a3;
+      t2 += (double)a2 * a2 + (double)a3 * a3;
     }
   }
-  for (; i < span; i += B) {
-    const f4 v = x4[addr(i)];
+  for (; i < b.span; i += B) {
+    const V v = x[b.addr(i)];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s1 += v[j];
-      s2 += (double)v[j] * v[j];
+    for (int j = 0; j < L; ++j) {
+      const double a = lane(v, j);
+      s1 += a;
+      s2 += a * a;
     }
   }
-  s1 += t1;
-  s2 += t2;
-  __shared__ double sh1[TPB], sh2[TPB];
-  sh1[threadIdx.x] = s1;
-  sh2[threadIdx.x] = s2;
-  __syncthreads();
-  for (int off = TPB / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) {
-      sh1[threadIdx.x] += sh1[threadIdx.x + off];
-      sh2[threadIdx.x] += sh2[threadIdx.x + off];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[(long)c * nb + slice] = {sh1[0], sh2[0]};
+  bn_reduce_store(s1 + t1, s2 + t2, b, nb, out);
 }
 
 void bn_fwd_stats(hipStream_t s, const float* x, int N, int C, long S,
                   int nb, void* partials) {
   PerfScope perf(PERF_CLASS("bn"), s, 0, 4.0 * N * C * S);
   if (S % 4 == 0) {
-    hipLaunchKernelGGL(k_bn_fwd_stats_v4, dim3(C * nb), dim3(TPB), 0, s,
+    hipLaunchKernelGGL(k_bn_fwd_stats<f4>, dim3(C * nb), dim3(TPB), 0, s,
                        (const f4*)x, N, C, (int)(S / 4), nb,
                        (double2*)partials);
     ktrace_bn(kBnFwdStats, kVarV4, N, nb, (int)(S / 4));
     return;
   }
-  hipLaunchKernelGGL(k_bn_fwd_stats, dim3(C * nb), dim3(TPB), 0, s, x, N, C,
-                     S, nb, (double2*)partials);
+  hipLaunchKernelGGL(k_bn_fwd_stats<float>, dim3(C * nb), dim3(TPB), 0, s, x,
+                     N, C, (int)S, nb, (double2*)partials);
   ktrace_bn(kBnFwdStats, kVarScalar, N, nb, S);
 }
 
@@ -816,8 +730,27 @@ void bn_fwd_finalize(hipStream_t s, const void* partials, int nb, int C,
                      inv_std);
 }
 
-// flat float4 walk; per 4-pack ONE division recovers the channel (packs
-// never straddle a channel boundary check: split handled elementwise)
+// The norm / apply kernels walk the tensor as flat float4 packs; per pack
+// ONE division recovers the channel.  A pack that straddles a channel
+// boundary (whole == false) takes the channel per element, from bn_chan.
+// 32-bit index math: the 64-bit division per 16B pack is ~3x the
+// instruction cost of the 32-bit one, and every count here fits uint32
+// (largest tensor ~300M elements).
+struct BnPack {
+  unsigned e0;  // first element
+  int c;        // its channel
+  bool whole;   // all four elements lie in channel c
+};
+__device__ __forceinline__ BnPack bn_pack(long i, int C, int S) {
+  const unsigned e0 = (unsigned)(i * 4);
+  const int row = (int)(e0 / (unsigned)S);  // n*C + c
+  const int rem = (int)(e0 - (unsigned)row * (unsigned)S);
+  return {e0, row % C, rem + 4 <= S};
+}
+__device__ __forceinline__ int bn_chan(unsigned e, int C, int S) {
+  return (int)((e / (unsigned)S) % (unsigned)C);
+}
+
 __global__ void k_bn_fwd_norm(const f4* __restrict__ x,
                               const float* __restrict__ mean,
                               const float* __restrict__ inv_std,
@@ -826,28 +759,27 @@ __global__ void k_bn_fwd_norm(const f4* __restrict__ x,
                               int S, int frelu, long n4,
                               const f4* __restrict__ add,
                               f4* __restrict__ y) {
+  struct Chan {
+    float mu, inv, sc, bi;
+  };
+  auto chan = [&](int c) {
+    return Chan{mean[c], inv_std[c], sb ? scale[c] : 1.f,
+                sb ? bias[c] : 0.f};
+  };
+  auto norm = [](float v, const Chan& k) {
+    return (v - k.mu) * k.inv * k.sc + k.bi;
+  };
   VEC_GRID(i, n4) {
-    // 32-bit index math: the 64-bit division per 16B pack is ~3x the
-    // instruction cost of the 32-bit one, and every count here fits
-    // uint32 (largest tensor ~300M elements)
-    const unsigned e0 = (unsigned)(i * 4);
-    const int row = (int)(e0 / (unsigned)S);  // n*C + c
-    const int c0 = row % C;
-    const int rem = (int)(e0 - (unsigned)row * (unsigned)S);
+    const BnPack p = bn_pack(i, C, S);
     f4 v = x[i];
-    if (rem + 4 <= S) {
-      const float mu = mean[c0], inv = inv_std[c0];
-      const float sc = sb ? scale[c0] : 1.f, bi = sb ? bias[c0] : 0.f;
+    if (p.whole) {
+      const Chan k = chan(p.c);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = (v[j] - mu) * inv * sc + bi;
-    } else {  // pack crosses a channel boundary
+      for (int j = 0; j < 4; ++j) v[j] = norm(v[j], k);
+    } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const unsigned e = e0 + j;
-        const int cc = (int)((e / (unsigned)S) % (unsigned)C);
-        v[j] = (v[j] - mean[cc]) * inv_std[cc] * (sb ? scale[cc] : 1.f) +
-               (sb ? bias[cc] : 0.f);
-      }
+      for (int j = 0; j < 4; ++j)
+        v[j] = norm(v[j], chan(bn_chan(p.e0 + j, C, S)));
     }
     if (add) {  // fused residual: bn(x) + other (ResNet block pattern)
       const f4 a = add[i];
@@ -920,133 +852,50 @@ void bn_fwd_test(hipStream_t s, const float* x, const float* gmean,
                      s, x, gmean, gvar, scale, bias, sb, N, C, S, eps, y);
 }
 
-__global__ void k_bn_bwd_stats(const float* __restrict__ x,
-                               const float* __restrict__ dy,
+template <typename V>
+__global__ void k_bn_bwd_stats(const V* __restrict__ x,
+                               const V* __restrict__ dy,
                                const float* __restrict__ mean,
                                const float* __restrict__ inv_std, int N,
-                               int C, long S, int nb,
+                               int C, int per, int nb,
                                const float* __restrict__ scale,
                                const float* __restrict__ bias, int frelu,
                                double2* __restrict__ out) {
-  const int c = blockIdx.x % C;
-  const int slice = blockIdx.x / C;
-  const int n0 = (int)((long)N * slice / nb);
-  const int n1 = (int)((long)N * (slice + 1) / nb);
-  const int Si = (int)S;
-  const int span = (n1 - n0) * Si;
+  constexpr int L = kLanes<V>;
+  const BnBlock b = bn_block(N, C, per, nb);
   const int B = blockDim.x;
-  const float m = mean[c], inv = inv_std[c];
+  const float m = mean[b.c], inv = inv_std[b.c];
   // fused ReLU backward: recompute the forward activation's sign exactly
   // (same fp32 op sequence as k_bn_fwd_norm) — no extra memory stream
-  const float sc = scale ? scale[c] : 1.f;
-  const float bi = bias ? bias[c] : 0.f;
-  auto addr = [&](int i) {
-    const int n = n0 + i / Si;
-    return ((long)n * C + c) * S + (i - (n - n0) * Si);
-  };
-  double s_dy = 0, s_dyxn = 0, t_dy = 0, t_dyxn = 0;
-  int i = threadIdx.x;
-  for (; i + B < span; i += 2 * B) {  // 4 loads (2 pairs) in flight
-    const long o0 = addr(i), o1 = addr(i + B);
-    const float xn0 = (x[o0] - m) * inv, xn1 = (x[o1] - m) * inv;
-    double d0 = dy[o0], d1 = dy[o1];
-    if (frelu && xn0 * sc + bi <= 0.f) d0 = 0.0;
-    if (frelu && xn1 * sc + bi <= 0.f) d1 = 0.0;
-    s_dy += d0;
-    s_dyxn += d0 * (double)xn0;
-    t_dy += d1;
-    t_dyxn += d1 * (double)xn1;
-  }
-  for (; i < span; i += B) {
-    const long off = addr(i);
-    const float xn = (x[off] - m) * inv;
-    double d = dy[off];
+  const float sc = scale ? scale[b.c] : 1.f;
+  const float bi = bias ? bias[b.c] : 0.f;
+  // one element into the pair (s_dy, s_dyxn)
+  auto add = [&](float xv, float dv, double& s_dy, double& s_dyxn) {
+    const float xn = (xv - m) * inv;
+    double d = dv;
     if (frelu && xn * sc + bi <= 0.f) d = 0.0;
     s_dy += d;
     s_dyxn += d * (double)xn;
-  }
-  s_dy += t_dy;
-  s_dyxn += t_dyxn;
-  __shared__ double sh1[TPB], sh2[TPB];
-  sh1[threadIdx.x] = s_dy;
-  sh2[threadIdx.x] = s_dyxn;
-  __syncthreads();
-  for (int off = TPB / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) {
-      sh1[threadIdx.x] += sh1[threadIdx.x + off];
-      sh2[threadIdx.x] += sh2[threadIdx.x + off];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[(long)c * nb + slice] = {sh1[0], sh2[0]};
-}
-__global__ void k_bn_bwd_stats_v4(const f4* __restrict__ x4,
-                                  const f4* __restrict__ dy4,
-                                  const float* __restrict__ mean,
-                                  const float* __restrict__ inv_std, int N,
-                                  int C, int S4, int nb,
-                                  const float* __restrict__ scale,
-                                  const float* __restrict__ bias, int frelu,
-                                  double2* __restrict__ out) {
-  const int c = blockIdx.x % C;
-  const int slice = blockIdx.x / C;
-  const int n0 = (int)((long)N * slice / nb);
-  const int n1 = (int)((long)N * (slice + 1) / nb);
-  const int span = (n1 - n0) * S4;
-  const int B = blockDim.x;
-  const float m = mean[c], inv = inv_std[c];
-  const float sc = scale ? scale[c] : 1.f;
-  const float bi = bias ? bias[c] : 0.f;
-  auto addr = [&](int i) {
-    const int n = n0 + i / S4;
-    return ((long)n * C + c) * S4 + (i - (n - n0) * S4);
   };
   double s_dy = 0, s_dyxn = 0, t_dy = 0, t_dyxn = 0;
   int i = threadIdx.x;
-  for (; i + B < span; i += 2 * B) {  // 4 loads (2 pairs) in flight
-    const long o0 = addr(i), o1 = addr(i + B);
-    const f4 xv0 = x4[o0], dv0 = dy4[o0];
-    const f4 xv1 = x4[o1], dv1 = dy4[o1];
+  for (; i + B < b.span; i += 2 * B) {  // 4 loads (2 pairs) in flight
+    const long o0 = b.addr(i), o1 = b.addr(i + B);
+    const V xv0 = x[o0], dv0 = dy[o0];
+    const V xv1 = x[o1], dv1 = dy[o1];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float xn0 = (xv0[j] - m) * inv;
-      const float xn1 = (xv1[j] - m) * inv;
-      double d0 = dv0[j], d1 = dv1[j];
-      if (frelu && xn0 * sc + bi <= 0.f) d0 = 0.0;
-      if (frelu && xn1 * sc + bi <= 0.f) d1 = 0.0;
-      s_dy += d0;
-      s_dyxn += d0 * (double)xn0;
-      t_dy += d1;
-      t_dyxn += d1 * (double)xn1;
+    for (int j = 0; j < L; ++j) {
+      add(lane(xv0, j), lane(dv0, j), s_dy, s_dyxn);
+      add(lane(xv1, j), lane(dv1, j), t_dy, t_dyxn);
     }
   }
-  for (; i < span; i += B) {
-    const long off = addr(i);
-    const f4 xv = x4[off];
-    const f4 dv = dy4[off];
+  for (; i < b.span; i += B) {
+    const long off = b.addr(i);
+    const V xv = x[off], dv = dy[off];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float xn = (xv[j] - m) * inv;
-      double d = dv[j];
-      if (frelu && xn * sc + bi <= 0.f) d = 0.0;
-      s_dy += d;
-      s_dyxn += d * (double)xn;
-    }
+    for (int j = 0; j < L; ++j) add(lane(xv, j), lane(dv, j), s_dy, s_dyxn);
   }
-  s_dy += t_dy;
-  s_dyxn += t_dyxn;
-  __shared__ double sh1[TPB], sh2[TPB];
-  sh1[threadIdx.x] = s_dy;
-  sh2[threadIdx.x] = s_dyxn;
-  __syncthreads();
-  for (int off = TPB / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) {
-      sh1[threadIdx.x] += sh1[threadIdx.x + off];
-      sh2[threadIdx.x] += sh2[threadIdx.x + off];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[(long)c * nb + slice] = {sh1[0], sh2[0]};
+  bn_reduce_store(s_dy + t_dy, s_dyxn + t_dyxn, b, nb, out);
 }
 
 void bn_bwd_stats(hipStream_t s, const float* x, const float* dy,
@@ -1055,15 +904,15 @@ void bn_bwd_stats(hipStream_t s, const float* x, const float* dy,
                   int frelu, void* partials) {
   PerfScope perf(PERF_CLASS("bn"), s, 0, 8.0 * N * C * S);
   if (S % 4 == 0) {
-    hipLaunchKernelGGL(k_bn_bwd_stats_v4, dim3(C * nb), dim3(TPB), 0, s,
+    hipLaunchKernelGGL(k_bn_bwd_stats<f4>, dim3(C * nb), dim3(TPB), 0, s,
                        (const f4*)x, (const f4*)dy, mean, inv_std, N, C,
                        (int)(S / 4), nb, scale, bias, frelu,
                        (double2*)partials);
     ktrace_bn(kBnBwdStats, kVarV4, N, nb, (int)(S / 4));
     return;
   }
-  hipLaunchKernelGGL(k_bn_bwd_stats, dim3(C * nb), dim3(TPB), 0, s, x, dy,
-                     mean, inv_std, N, C, S, nb, scale, bias, frelu,
+  hipLaunchKernelGGL(k_bn_bwd_stats<float>, dim3(C * nb), dim3(TPB), 0, s, x,
+                     dy, mean, inv_std, N, C, (int)S, nb, scale, bias, frelu,
                      (double2*)partials);
   ktrace_bn(kBnBwdStats, kVarScalar, N, nb, S);
 }
@@ -1107,14 +956,22 @@ __global__ void k_bn_bwd_apply(const f4* __restrict__ x,
                                const float* __restrict__ m_dyxn,
                                const float* __restrict__ bias, int frelu,
                                int C, int S, long n4, f4* __restrict__ dx) {
+  // dx of one element of channel c; the fused ReLU's sign test is
+  // k_bn_fwd_norm's expression, op for op
+  // The per-element formula stands twice on purpose.  The
+  // compiler contracts dj * sc - mdy - mdyxn * xn into FMAs in the whole-pack
+  // path (hoisted values, branch-free: four elements vectorise into packed
+  // FMAs) and leaves it as multiplies and subtractions in the straddle path
+  // (the bias load sits behind frelu, mid-element).  Written once, as a
+  // function of hoisted values or of c, both paths round the same way, which
+  // moves the last bits of dx wherever S % 4 != 0 (the 7x7 stage): results
+  // are pinned bit for bit by bench.py --dump-outputs.
   VEC_GRID(i, n4) {
-    const unsigned e0 = (unsigned)(i * 4);
-    const int row = (int)(e0 / (unsigned)S);
-    const int rem = (int)(e0 - (unsigned)row * (unsigned)S);
+    const BnPack p = bn_pack(i, C, S);
     const f4 xv = x[i];
     f4 d = dy[i];
-    if (rem + 4 <= S) {
-      const int c = row % C;
+    if (p.whole) {
+      const int c = p.c;
       const float mu = mean[c], inv = inv_std[c];
       const float sc = sb ? scale[c] : 1.f;
       const float bi = (frelu && bias) ? bias[c] : 0.f;
@@ -1129,7 +986,7 @@ __global__ void k_bn_bwd_apply(const f4* __restrict__ x,
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int cc = (int)(((e0 + j) / (unsigned)S) % (unsigned)C);
+        const int cc = bn_chan(p.e0 + j, C, S);
         const float xn = (xv[j] - mean[cc]) * inv_std[cc];
         const float scc = sb ? scale[cc] : 1.f;
         float dj = d[j];
@@ -1159,6 +1016,24 @@ void bn_bwd_apply(hipStream_t s, const float* x, const float* dy,
 // coalesced: the single running cross-channel window was a serial
 // load->accumulate chain (SQ: 66% parked) — interleaving two independent
 // chains doubles the loads in flight (lrn_layer.cu:9-60 restated)
+// the pair of thread i: positions i and i + half of the N*S (n, s)
+// positions, as the offsets b0, b1 of their channel 0; the odd last thread
+// has one (two == false) and reads b1 = b0 without storing it
+struct LrnPair {
+  long b0, b1;
+  bool two;
+};
+__device__ __forceinline__ LrnPair lrn_pair(long i, long half, long total,
+                                            int C, long S) {
+  const long idx0 = i;
+  const long idx1 = i + half;
+  const bool two = idx1 < total;
+  const int n0 = (int)(idx0 / S);
+  const int n1 = two ? (int)(idx1 / S) : n0;
+  const long b0 = (long)n0 * C * S + (idx0 - (long)n0 * S);
+  const long b1 = two ? (long)n1 * C * S + (idx1 - (long)n1 * S) : b0;
+  return {b0, b1, two};
+}
 __global__ void k_lrn_fwd(const float* __restrict__ x, int N, int C, long S,
                           int size, float aos, float beta, float k,
                           float* __restrict__ scale, float* __restrict__ y) {
@@ -1166,13 +1041,9 @@ __global__ void k_lrn_fwd(const float* __restrict__ x, int N, int C, long S,
   const long half = (total + 1) / 2;
   const int pre = (size - 1) / 2;
   GRID_STRIDE(i, half) {
-    const long idx0 = i;
-    const long idx1 = i + half;
-    const bool two = idx1 < total;
-    const int n0 = (int)(idx0 / S);
-    const int n1 = two ? (int)(idx1 / S) : n0;
-    const long b0 = (long)n0 * C * S + (idx0 - (long)n0 * S);
-    const long b1 = two ? (long)n1 * C * S + (idx1 - (long)n1 * S) : b0;
+    const LrnPair pp = lrn_pair(i, half, total, C, S);
+    const long b0 = pp.b0, b1 = pp.b1;
+    const bool two = pp.two;
     float a0 = 0.f, a1 = 0.f;
     for (int c = 0; c < size - pre && c < C; ++c) {
       const float v0 = x[b0 + (long)c * S];
@@ -1224,13 +1095,9 @@ __global__ void k_lrn_fwd_t(const float* __restrict__ x, int N, int C,
   const long total = (long)N * S;
   const long half = (total + 1) / 2;
   GRID_STRIDE(i, half) {
-    const long idx0 = i;
-    const long idx1 = i + half;
-    const bool two = idx1 < total;
-    const int n0 = (int)(idx0 / S);
-    const int n1 = two ? (int)(idx1 / S) : n0;
-    const long b0 = (long)n0 * C * S + (idx0 - (long)n0 * S);
-    const long b1 = two ? (long)n1 * C * S + (idx1 - (long)n1 * S) : b0;
+    const LrnPair pp = lrn_pair(i, half, total, C, S);
+    const long b0 = pp.b0, b1 = pp.b1;
+    const bool two = pp.two;
     // ring[j] at top of iter c holds channel c-1-pre+j's raw value /
     // square = window(c-1); out-of-range channels are zero
     float q0[SZ], q1[SZ], v0[SZ], v1[SZ];
@@ -1351,13 +1218,9 @@ __global__ void k_lrn_bwd_t(const float* __restrict__ x,
   const long total = (long)N * S;
   const long half = (total + 1) / 2;
   GRID_STRIDE(i, half) {
-    const long idx0 = i;
-    const long idx1 = i + half;
-    const bool two = idx1 < total;
-    const int n0 = (int)(idx0 / S);
-    const int n1 = two ? (int)(idx1 / S) : n0;
-    const long b0 = (long)n0 * C * S + (idx0 - (long)n0 * S);
-    const long b1 = two ? (long)n1 * C * S + (idx1 - (long)n1 * S) : b0;
+    const LrnPair pp = lrn_pair(i, half, total, C, S);
+    const long b0 = pp.b0, b1 = pp.b1;
+    const bool two = pp.two;
     // rings hold channels [c-ctr, c+pre-1] at top of iter c
     float rr0[SZ - 1], rr1[SZ - 1], tt0[SZ - 1], tt1[SZ - 1];
     float a0 = 0.f, a1 = 0.f;
@@ -1699,31 +1562,18 @@ void dropout_bwd(hipStream_t s, const float* dy, const uint8_t* mask, long n,
 }
 
 // ------------------------------------------------------------ SGD
-__global__ void k_sgd(long n4, f4* __restrict__ g, f4* __restrict__ w,
-                      f4* __restrict__ h, float mom, float lr, float decay,
-                      float gscale) {
-  VEC_GRID(i, n4) {
-    f4 gv = g[i], wv = w[i], hv = h[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float gi = gv[j] * gscale + decay * wv[j];
-      gi = hv[j] = mom * hv[j] + lr * gi;
-      wv[j] -= gi;
-    }
-    w[i] = wv;
-    h[i] = hv;
-    g[i] = f4{0.f, 0.f, 0.f, 0.f};
+// the segment of arena offset i: the largest k with seg_off[k] <= i
+__device__ __forceinline__ int seg_find(const long* __restrict__ seg_off,
+                                        int nseg, long i) {
+  int a = 0, b = nseg - 1;
+  while (a < b) {
+    const int m = (a + b + 1) >> 1;
+    if (seg_off[m] <= i)
+      a = m;
+    else
+      b = m - 1;
   }
-}
-void sgd_update(hipStream_t s, long n, float* g, float* w, float* h,
-                float mom, float lr, float decay, float gscale) {
-  // arena offsets are 16-float aligned and blob memory is 64B-padded, so
-  // the float4 body may run over the pad (pad floats update to garbage in
-  // h; g pad stays 0; w pad unused) — correct for all live elements
-  PerfScope perf(PERF_CLASS("sgd"), s, 0, 20.0 * n);
-  const long n4 = (n + 3) / 4;
-  hipLaunchKernelGGL(k_sgd, dim3(nblocks(n4, 4)), dim3(TPB), 0, s, n4,
-                     (f4*)g, (f4*)w, (f4*)h, mom, lr, decay, gscale);
+  return a;
 }
 
 // segmented fused SGD: one launch covers a whole bucket's params.
@@ -1740,15 +1590,7 @@ __global__ void k_sgd_seg(long lo, long hi, float* __restrict__ g_arena,
                           float mom, float lr, float decay, float gscale) {
   for (long i = lo + blockIdx.x * (long)blockDim.x + threadIdx.x; i < hi;
        i += (long)gridDim.x * blockDim.x) {
-    // binary search: largest k with seg_off[k] <= i
-    int a = 0, b = nseg - 1;
-    while (a < b) {
-      const int m = (a + b + 1) >> 1;
-      if (seg_off[m] <= i)
-        a = m;
-      else
-        b = m - 1;
-    }
+    const int a = seg_find(seg_off, nseg, i);
     float* w = w_ptrs[a] + (i - seg_off[a]);
     float gi = g_arena[i] * gscale + (decay * decay_mults[a]) * *w;
     gi = h_arena[i] = mom * h_arena[i] + (lr * lr_mults[a]) * gi;
@@ -1793,15 +1635,7 @@ __global__ void k_solver_seg(long lo4, long hi4, f4* __restrict__ g_arena,
   for (long p = lo4 + blockIdx.x * (long)blockDim.x + threadIdx.x; p < hi4;
        p += (long)gridDim.x * blockDim.x) {
     const long i = 4 * p;
-    // binary search: largest k with seg_off[k] <= i
-    int a = 0, b = nseg - 1;
-    while (a < b) {
-      const int m = (a + b + 1) >> 1;
-      if (seg_off[m] <= i)
-        a = m;
-      else
-        b = m - 1;
-    }
+    const int a = seg_find(seg_off, nseg, i);
     f4* wp = (f4*)(w_ptrs[a] + (i - seg_off[a]));
     const float lr = c.lr * lr_mults[a];
     const float decay = c.decay * decay_mults[a];

@@ -316,11 +316,8 @@ void dropout_bwd(hipStream_t s, const float* dy, const uint8_t* mask, long n,
                  float scale, float* dx);
 
 // fused SGD update (reference sgd_solver.cu:10-20 + the 1/nranks scale of
-// net.cpp:910): g = g*gscale + decay*w; h = mom*h + lr*g; w -= h; g = 0.
-void sgd_update(hipStream_t s, long n, float* g, float* w, float* h,
-                float mom, float lr, float decay, float gscale);
-
-// segmented fused SGD over a flat arena range (one launch per bucket);
+// net.cpp:910): g = g*gscale + decay*w; h = mom*h + lr*g; w -= h; g = 0,
+// segmented over a flat arena range (one launch per bucket);
 // lrs/decays already folded with the per-param multipliers by the caller
 void sgd_update_segmented(hipStream_t s, long lo, long hi, float* g_arena,
                           float* h_arena, const long* seg_off,

@@ -233,11 +233,18 @@ def bn_inputs(r, N, C, H, W, mean=0.0, std=1.0):
 
 
 def check_bn(mode, N=4, C=6, H=5, W=5, scale_bias=True, mean=0.0, std=1.0,
-             eps=1e-4, seed=None, errs=None):
+             eps=1e-4, seed=None, errs=None, relu=False):
     """mean, std: of the normal input.  seed: draw the inputs from a
     generator of their own, bn_inputs(default_rng(seed), ...), so that a
     test can restate them.  errs receives the measured relerr of y / dx /
     dscale / dbias before each is asserted.
+
+    relu: an in-place ReLU follows on "out" (in GPU mode the net folds it
+    into the BN kernels, forward and backward; in CPU mode it runs as a
+    layer).  The reference is max(y_ref, 0), and the oracle's backward gets
+    dy zeroed where y_ref <= 0.  The oracle's y must stay 5e-5 clear of 0
+    (the fp32 forward is within about 1.5e-6 of it), so that no sign can
+    differ between the fp32 and the fp64 forward.
 
     The default input (unit variance, eps 1e-4) cannot see eps: the oracle
     with eps = 0 differs from the true output by relerr 3.7e-5, below TOL.
@@ -257,15 +264,24 @@ def check_bn(mode, N=4, C=6, H=5, W=5, scale_bias=True, mean=0.0, std=1.0,
     scale_bias: {"true" if scale_bias else "false"}
   }}
 }}"""
+    if relu:
+        body += '\nlayer { name: "relu" type: "ReLU" bottom: "out" top: "out" }'
     y_ref, _, _, inv_std, xnorm = orc.bn_fwd_train(
         x, eps, sc if scale_bias else None, bi if scale_bias else None)
+    if relu:
+        assert np.abs(y_ref).min() >= 5e-5, np.abs(y_ref).min()
+        # the engine gets the whole dy: masking it is the ReLU's work
+        dy_ref = np.where(y_ref <= 0, 0, dy).astype(np.float32)
+        y_ref = np.maximum(y_ref, 0)
+    else:
+        dy_ref = dy
     # learnable params of BN are [scale, bias] (stats blobs skipped)
     params = [sc, bi] if scale_bias else None
     net, y = run_layer(mode, [(N, C, H, W)], body, [x], params=params,
                        top_diff=dy)
     errs["y"] = relerr(y, y_ref)
     assert errs["y"] < TOL, f"bn fwd {errs['y']}"
-    dx_ref, dsc_ref, dbi_ref = orc.bn_bwd(xnorm, dy, inv_std,
+    dx_ref, dsc_ref, dbi_ref = orc.bn_bwd(xnorm, dy_ref, inv_std,
                                           sc if scale_bias else None)
     errs["dx"] = relerr(net.blob("in0", diff=True), dx_ref)
     assert errs["dx"] < TOL, f"bn dx {errs['dx']}"

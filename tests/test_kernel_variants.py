@@ -158,6 +158,16 @@ BN_CASES = {
     # E[x^2] - m^2 cancellation (2501 - 2500)
     "B7": (dict(N=4, C=6, H=8, W=8, mean=50.0, std=1.0),
            "var=v4 nb=4 span_max=16"),
+    # fused in-place ReLU (named to sort after B7: the rows above keep their
+    # seeds): the backward statistics and apply kernels recompute the
+    # activation's sign, in the v4 and the scalar kernel and, with B4's
+    # shape, on packs that straddle a channel.  The fused ReLU launches
+    # nothing, so the trace is the unfused one.
+    "R1": (dict(_B1, relu=True), "var=v4 nb=2 span_max=1056"),
+    "R2": (dict(N=2, C=3, H=33, W=33, relu=True),
+           "var=scalar nb=2 span_max=1089"),
+    "R3": (dict(N=5, C=600, H=1, W=3, relu=True),
+           "var=scalar nb=3 span_max=6"),
 }
 
 
