@@ -77,6 +77,18 @@ void DeviceAllocator::free_all() {
   free_.clear();
 }
 
+void* DeviceBuf::reserve(size_t want) {
+  if (want > bytes) {
+    if (p) Engine::get().dalloc.release(p, bytes);
+    p = Engine::get().dalloc.alloc(want);
+    bytes = want;
+  }
+  return p;
+}
+DeviceBuf::~DeviceBuf() {
+  if (p) Engine::get().dalloc.release(p, bytes);
+}
+
 SyncedMemory::~SyncedMemory() {
   if (cpu_ptr_) free(cpu_ptr_);
   if (gpu_ptr_ && own_gpu_)

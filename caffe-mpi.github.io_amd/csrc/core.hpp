@@ -114,6 +114,21 @@ class DeviceAllocator {
   std::mutex mu_;
 };
 
+// A device buffer that one object owns and keeps across calls (a conv
+// layer's cached col buffer, the data feed's upload targets).  It comes
+// from Engine::dalloc, so it has the allocator's +64 B tail; it grows only
+// when asked for more (the old contents are dropped), has no host mirror
+// and is never zero-filled; the owner's destructor returns it to dalloc.
+struct DeviceBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  void* reserve(size_t want);  // p, grown first when want > bytes
+  DeviceBuf() = default;
+  DeviceBuf(const DeviceBuf&) = delete;
+  DeviceBuf& operator=(const DeviceBuf&) = delete;
+  ~DeviceBuf();
+};
+
 struct PerfClass {
   std::atomic<long> launches{0};
   std::atomic<double> flops{0};

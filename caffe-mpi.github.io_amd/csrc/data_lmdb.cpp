@@ -110,6 +110,10 @@ struct LmdbFeed {
   int* pin_geo[2] = {nullptr, nullptr};
   float* pin_lab[2] = {nullptr, nullptr};
   hipEvent_t ev[2] = {nullptr, nullptr};
+  // device side of the upload, owned by the feed: the uint8 batch and its
+  // geometry (rewritten every iteration) and the mean (uploaded once)
+  DeviceBuf dev_u8, dev_geo, dev_mean;
+  bool mean_uploaded = false;
 
   ~LmdbFeed() {
     {
@@ -327,15 +331,8 @@ void DataLayer::forward_lmdb_gpu(const std::vector<Blob*>& top) {
   memcpy(F.pin_u8[p], slot.data.data(), usz);
   memcpy(F.pin_geo[p], slot.geo.data(), sizeof(int) * slot.geo.size());
   memcpy(F.pin_lab[p], slot.labels.data(), sizeof(float) * batch_);
-  Workspace& ws = Workspace::get_global();
-  if (u8_slot_ < 0) {
-    static int next_slot = 300;
-    u8_slot_ = next_slot++;
-    geo_slot_ = next_slot++;
-    mean_slot_ = next_slot++;
-  }
-  uint8_t* du8 = (uint8_t*)ws.get(u8_slot_, usz);
-  int* dgeo = (int*)ws.get(geo_slot_, sizeof(int) * slot.geo.size());
+  uint8_t* du8 = (uint8_t*)F.dev_u8.reserve(usz);
+  int* dgeo = (int*)F.dev_geo.reserve(sizeof(int) * slot.geo.size());
   HIP_CHECK(hipMemcpyAsync(du8, F.pin_u8[p], usz, hipMemcpyHostToDevice,
                            E.stream));
   HIP_CHECK(hipMemcpyAsync(dgeo, F.pin_geo[p],
@@ -343,12 +340,12 @@ void DataLayer::forward_lmdb_gpu(const std::vector<Blob*>& top) {
                            hipMemcpyHostToDevice, E.stream));
   float* dmean = nullptr;
   if (!F.mean.empty()) {
-    dmean = (float*)ws.get(mean_slot_, sizeof(float) * F.mean.size());
-    if (!mean_uploaded_) {
+    dmean = (float*)F.dev_mean.reserve(sizeof(float) * F.mean.size());
+    if (!F.mean_uploaded) {
       HIP_CHECK(hipMemcpy(dmean, F.mean.data(),
                           sizeof(float) * F.mean.size(),
                           hipMemcpyHostToDevice));
-      mean_uploaded_ = true;
+      F.mean_uploaded = true;
     }
   }
   gpu::transform_u8(E.stream, du8, batch_, F.dc, F.dh, F.dw, F.outH,

@@ -720,7 +720,7 @@ void gemm(hipStream_t s, bool transA, bool transB, long M, long N, long K,
 
   if (r.sk > 1) {  // split-K: partial slabs, then the fixed-order reduce
     g.slab = (float*)Workspace::get_global().get(
-        10, sizeof(float) * (size_t)r.sk * M * N);
+        Workspace::kSplitK, sizeof(float) * (size_t)r.sk * M * N);
     g.SK = r.sk;
   }
   const dim3 grid((unsigned)g.tiles, 1, (unsigned)r.sk);
@@ -829,7 +829,7 @@ void bias_grad(hipStream_t s, const float* dy, int N, int C, long S,
   PerfScope perf(PERF_CLASS("reduce"), s, 0, 4.0 * N * C * S);
   const int nb = std::max(1, std::min(N, 2048 / std::max(1, C)));
   double* part = (double*)Workspace::get_global().get(
-      12, sizeof(double) * (size_t)C * nb);
+      Workspace::kBiasPart, sizeof(double) * (size_t)C * nb);
   hipLaunchKernelGGL(k_bias_grad_part, dim3(C * nb), dim3(256), 0, s, dy, N,
                      C, (int)S, nb, part);
   hipLaunchKernelGGL(k_bias_grad_fin, dim3(1), dim3(256), 0, s, part, nb, C,

@@ -129,10 +129,21 @@ std::shared_ptr<Layer> create_layer(const PMsgPtr& param);
 // xavier/msra; CPU-side mt19937, seed = engine.seed + rank)
 void fill_blob(Blob& b, const PMsgPtr& filler, std::mt19937_64& rng);
 
-// shared grow-only device/host workspaces (conv col buffers etc.), the
-// reference's GPUMemory::Workspace analog (util/gpu_memory.hpp:76-127)
+// shared grow-only scratch, the reference's GPUMemory::Workspace analog
+// (util/gpu_memory.hpp:76-127).  Scratch only: a slot's contents last until
+// the next get() of that slot by anyone.  What has to outlive the call that
+// filled it (a conv layer's cached col buffer, the data feed's upload
+// targets) is a DeviceBuf member of its owner, never a slot here.
 struct Workspace {
-  void* get(int slot, size_t bytes);  // device (GPU mode) / host (CPU mode)
+  enum Slot {
+    kCpuCol,    // CPU conv: one image's col matrix
+    kDcol,      // conv dgrad: dcol = Wᵀ·dY ahead of col2im (CPU: one image)
+    kSplitK,    // gemm(): split-K partial slabs
+    kFlipW,     // conv dgrad: flipped/transposed weights
+    kBiasPart,  // bias_grad(): per-slice double partials
+    kNumSlots
+  };
+  void* get(Slot slot, size_t bytes);  // device (GPU mode) / host (CPU mode)
   static Workspace& get_global();
   ~Workspace();
 
@@ -142,7 +153,7 @@ struct Workspace {
     size_t bytes = 0;
     bool device = false;
   };
-  std::map<int, Buf> bufs_;
+  Buf bufs_[kNumSlots];
   std::mutex mu_;
 };
 
@@ -177,9 +188,7 @@ class DataLayer : public Layer {  // synthetic or LMDB source (§8a a12,
   void setup_lmdb(const std::string& source);
   void forward_lmdb_cpu(const std::vector<Blob*>& top);
   void forward_lmdb_gpu(const std::vector<Blob*>& top);
-  std::shared_ptr<LmdbFeed> feed_;
-  int u8_slot_ = -1, geo_slot_ = -1, mean_slot_ = -1;
-  bool mean_uploaded_ = false;
+  std::shared_ptr<LmdbFeed> feed_;  // owns its device upload buffers
 };
 
 class ConvolutionLayer : public Layer {
@@ -196,18 +205,24 @@ class ConvolutionLayer : public Layer {
                     const std::vector<Blob*>&) override;
   void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
                     const std::vector<Blob*>&) override;
-  // strided 1x1 dgrad without a col2im pass (zero + strided-scatter GEMM)
-  void scatter_dgrad(const std::vector<Blob*>& top,
-                     const std::vector<Blob*>& bottom);
 
   int Cout_ = 0, kh_ = 0, kw_ = 0, sh_ = 1, sw_ = 1, ph_ = 0, pw_ = 0,
       dh_ = 1, dw_ = 1, group_ = 1;
   bool bias_ = true;
   int N_ = 0, C_ = 0, H_ = 0, W_ = 0, OH_ = 0, OW_ = 0;
-  long S_ = 0, Spad_ = 0;  // spatial count and 64-padded count
-  int col_slot_ = -1;      // per-layer cached col buffer (fwd fills,
-                           // bwd reuses — no im2col recompute)
+  long S_ = 0, Spad_ = 0;  // spatial count and 16-padded count
   bool fuse_relu_ = false;  // in-place ReLU folded into the GEMM epilogue
+
+  // GPU plan, decided once per Reshape by plan_gpu() (layers_gpu.cpp, with
+  // the policy): how forward and wgrad read x, and how dgrad is done.
+  // Forward_gpu and Backward_gpu switch on it and never re-derive it.
+  enum XOperand { kChanView, kIm2colView, kExplicitCol };
+  enum Dgrad { kTnScatter, kFlipConv, kStridedScatter, kCol2im };
+  XOperand xop_ = kExplicitCol;
+  Dgrad dgrad_ = kCol2im;
+  void plan_gpu();
+  DeviceBuf col_;  // kExplicitCol: cached col buffer [C*kh*kw][N*Spad]
+                   // (forward fills, backward reuses — no im2col recompute)
 };
 
 class InnerProductLayer : public Layer {

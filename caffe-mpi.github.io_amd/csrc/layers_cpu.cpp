@@ -103,7 +103,7 @@ Workspace& Workspace::get_global() {
   static Workspace w;
   return w;
 }
-void* Workspace::get(int slot, size_t bytes) {
+void* Workspace::get(Slot slot, size_t bytes) {
   std::lock_guard<std::mutex> g(mu_);
   Buf& b = bufs_[slot];
   const bool want_dev = Engine::get().mode == Mode::GPU;
@@ -123,8 +123,8 @@ void* Workspace::get(int slot, size_t bytes) {
   return b.p;
 }
 Workspace::~Workspace() {
-  for (auto& kv : bufs_)
-    if (kv.second.p && !kv.second.device) free(kv.second.p);
+  for (Buf& b : bufs_)
+    if (b.p && !b.device) free(b.p);
 }
 
 
@@ -243,13 +243,14 @@ void ConvolutionLayer::Reshape(const std::vector<Blob*>& bottom,
   // image and padding waste is <= 15 columns per image
   Spad_ = (S_ + 15) / 16 * 16;
   top[0]->Reshape({N_, Cout_, OH_, OW_});
+  plan_gpu();
 }
 
 void ConvolutionLayer::Forward_cpu(const std::vector<Blob*>& bottom,
                                    const std::vector<Blob*>& top) {
   const int K = C_ / group_ * kh_ * kw_;
   float* col = (float*)Workspace::get_global().get(
-      0, sizeof(float) * (size_t)C_ * kh_ * kw_ * S_);
+      Workspace::kCpuCol, sizeof(float) * (size_t)C_ * kh_ * kw_ * S_);
   const float* x = bottom[0]->cpu_data();
   const float* w = blobs_[0]->cpu_data();
   float* y = top[0]->mutable_cpu_data();
@@ -280,8 +281,9 @@ void ConvolutionLayer::Backward_cpu(const std::vector<Blob*>& top,
                                     const std::vector<Blob*>& bottom) {
   const int K = C_ / group_ * kh_ * kw_;
   const size_t colbytes = sizeof(float) * (size_t)C_ * kh_ * kw_ * S_;
-  float* col = (float*)Workspace::get_global().get(0, colbytes);
-  float* dcol = (float*)Workspace::get_global().get(1, colbytes);
+  Workspace& ws = Workspace::get_global();
+  float* col = (float*)ws.get(Workspace::kCpuCol, colbytes);
+  float* dcol = (float*)ws.get(Workspace::kDcol, colbytes);
   const float* x = bottom[0]->cpu_data();
   const float* w = blobs_[0]->cpu_data();
   const float* dy = top[0]->cpu_diff();

@@ -4,9 +4,9 @@
 // reference's per-image GEMM loop conv_layer.cu:14-21 which is
 // launch/sync-bound): whole-batch GEMMs, NCHW-view operands (implicit
 // im2col for s1/d1 at OW>=24), fused bias/ReLU/scatter epilogues, explicit
-// cached col buffers only for strided/small-OW convs.
-// Workspace slots: 1 = dcol, 10 = split-K slabs, 11 = flipped weights,
-// 12 = bias-grad partials, 100+ = per-conv-layer cached col buffers.
+// cached col buffers only for strided/small-OW convs.  Shared scratch comes
+// from the named Workspace slots (layers.hpp); a buffer that outlives a call
+// is owned by its layer.
 #include "layers.hpp"
 
 namespace camd {
@@ -33,78 +33,76 @@ void DataLayer::Forward_gpu(const std::vector<Blob*>&,
 
 // ------------------------------------------------------------------ Conv
 // MI355X-first conv, two paths:
-//  - IMPLICIT GEMM (stride 1, dilation 1 — every conv that needs
-//    backward-data in the four models): the GEMM staging reads x / dY
-//    straight from NCHW through im2col/NCHW views; no col buffer, no
-//    im2col/col2im kernels; backward-data runs as a forward convolution
-//    over dY with flipped/transposed weights (Wt), scattered into dx.
-//  - explicit batched col buffer [K][N*Spad] for strided convs (cached per
-//    layer: forward fills, backward reuses).
-static bool conv_s1d1(const ConvolutionLayer& l) {
-  return l.sh_ == 1 && l.sw_ == 1 && l.dh_ == 1 && l.dw_ == 1;
-}
-// implicit-im2col staging walks pixel chunks of 16; below OW 24 nearly
-// every chunk crosses an output row (slow masked path) — the explicit col
-// buffer wins there (measured: stage-4 3x3 at OW=14 ran at 68 vs ~90 TF).
-// Round 2: strides are supported by the view, but ONLY for conv1-like
-// shapes (kh>1, Cout/group <= 128 so the x view is staged once — a
-// strided view re-read per output tile-row pays 2x bytes per pass, which
-// measured SLOWER than the explicit col for the large-Cout 1x1/s2
-// projections).  Strided 1x1 keeps the explicit col for fwd/wgrad and a
-// zero+scatter dgrad (no dcol GEMM, no col2im).  Dilation stays explicit.
-static bool conv_implicit(const ConvolutionLayer& l) {
+//  - IMPLICIT GEMM: the GEMM staging reads x / dY straight from NCHW through
+//    im2col/NCHW views; no col buffer, no im2col/col2im kernels; at stride 1
+//    backward-data runs as a forward convolution over dY with
+//    flipped/transposed weights (Wt), scattered into dx.
+//  - explicit batched col buffer [K][N*Spad], cached per layer (forward
+//    fills, backward reuses).
+// plan_gpu() decides which, once per Reshape (table in DESIGN.md §3).  The
+// implicit-im2col staging walks pixel chunks of 16; below OW 24 nearly every
+// chunk crosses an output row (slow masked path) — the explicit col wins
+// there (measured: stage-4 3x3 at OW=14 ran at 68 vs ~90 TF).  Strides are
+// supported by the view, but
+// ONLY for conv1-like shapes (kh>1, Cout/group <= 128 so the x view is
+// staged once — a strided view re-read per output tile-row pays 2x bytes
+// per pass, which measured SLOWER than the explicit col for the large-Cout
+// 1x1/s2 projections).  Strided 1x1 p0 keeps the explicit col for fwd/wgrad
+// and a zero+scatter dgrad (no dcol GEMM, no col2im: it writes only the
+// sampled input pixels).  Dilation stays explicit.  The strided scatter
+// never meets the im2col view — a strided view needs kh > 1, the scatter
+// kh == 1 — so it is tested on its own, after the stride-1 view.
+void ConvolutionLayer::plan_gpu() {
   static const int min_ow = [] {
     const char* e = getenv("CAFFE_IMPLICIT_MIN_OW");
     return e ? atoi(e) : 24;
   }();
-  if (l.dh_ != 1 || l.dw_ != 1) return false;
-  if (l.sh_ == 1 && l.sw_ == 1) return l.kh_ == 1 || l.OW_ >= min_ow;
   static const bool strided_ok = [] {
     const char* e = getenv("CAFFE_IMPLICIT_STRIDED");
     return e ? atoi(e) != 0 : true;
   }();
-  return strided_ok && l.kh_ > 1 && l.OW_ >= min_ow &&
-         l.Cout_ / l.group_ <= 128;
-}
-// strided 1x1 pad-0 dgrad can always scatter (writes only the sampled
-// input pixels after a zero fill) — independent of the fwd/wgrad path
-static bool conv_scatter_dgrad(const ConvolutionLayer& l) {
-  return (l.sh_ > 1 || l.sw_ > 1) && l.kh_ == 1 && l.kw_ == 1 &&
-         l.ph_ == 0 && l.pw_ == 0 && l.dh_ == 1 && l.dw_ == 1;
-}
-static bool conv_is_1x1(const ConvolutionLayer& l) {
-  return l.kh_ == 1 && l.kw_ == 1 && conv_s1d1(l) && !l.ph_ && !l.pw_ &&
-         l.group_ == 1;
+  const bool s1 = sh_ == 1 && sw_ == 1, d1 = dh_ == 1 && dw_ == 1;
+  const bool k1p0 = kh_ == 1 && kw_ == 1 && !ph_ && !pw_;
+  const bool chan = k1p0 && s1 && d1 && group_ == 1;
+  const bool view =
+      !chan && d1 &&
+      (s1 ? kh_ == 1 || OW_ >= min_ow
+          : strided_ok && kh_ > 1 && OW_ >= min_ow && Cout_ / group_ <= 128);
+  xop_ = chan ? kChanView : view ? kIm2colView : kExplicitCol;
+  dgrad_ = chan                ? kTnScatter
+           : view && s1        ? kFlipConv
+           : !s1 && k1p0 && d1 ? kStridedScatter
+                               : kCol2im;
 }
 
-// strided 1x1 (projection shortcuts) dgrad: dgrad touches only the sampled
-// input pixels — zero dx, then a GEMM whose epilogue scatters column
-// (oh, ow) to input pixel (oh*sh, ow*sw).  No dcol round-trip, no col2im.
-void ConvolutionLayer::scatter_dgrad(const std::vector<Blob*>& top,
-                                     const std::vector<Blob*>& bottom) {
-  Engine& E = Engine::get();
-  const int K = C_ / group_ * kh_ * kw_;
-  const long NS = (long)N_ * Spad_;
-  const float* w = blobs_[0]->gpu_data();
-  const float* dy = top[0]->gpu_diff();
-  GemmView dyv{Spad_, S_, Cout_};
-  float* dx = bottom[0]->mutable_gpu_diff();
-  gpu::set_const(E.stream, bottom[0]->count(), 0.f, dx);
+// elements in one group's slice of each conv operand (group g's slice starts
+// g of them in): w = W, dW and the flipped weights; x = x, dx; y = y, dy;
+// col = col, dcol, whose rows are ns = N*Spad long
+struct ConvGroup {
+  long w, x, y, bias, col;
+};
+static ConvGroup conv_group(const ConvolutionLayer& l, long ns) {
+  const long cig = l.C_ / l.group_, cog = l.Cout_ / l.group_;
+  const long K = cig * l.kh_ * l.kw_;
+  return {cog * K, cig * l.H_ * l.W_, cog * l.S_, cog, K * ns};
+}
+
+// NCHW-scatter epilogue: column n*spad + s of GEMM row r lands at
+// C[(n*chan + r)*S + s]
+static GemmEpi nchw_scatter(long spad, long S, long chan) {
   GemmEpi epi;
-  epi.spad = Spad_;
-  epi.S = S_;
-  epi.n_stride = (long)C_ * H_ * W_;
-  epi.Srow = (long)H_ * W_;
-  epi.OWo = OW_;
-  epi.osh = sh_;
-  epi.osw = sw_;
-  epi.Wd = W_;
-  for (int g = 0; g < group_; ++g)
-    gpu::gemm(E.stream, true, false, C_ / group_, NS, Cout_ / group_, 1.f,
-              w + (long)g * (Cout_ / group_) * K, K,
-              dy + (long)g * (Cout_ / group_) * S_, 0, 0.f,
-              dx + (long)g * (C_ / group_) * H_ * W_, 0, &epi, nullptr,
-              &dyv);
+  epi.spad = spad;
+  epi.S = S;
+  epi.n_stride = chan * S;
+  return epi;
+}
+
+// x as forward's and wgrad's B operand: the plan's view (the explicit col
+// passes its buffer as a plain B instead and no view)
+static GemmView conv_x_view(const ConvolutionLayer& l) {
+  if (l.xop_ == ConvolutionLayer::kChanView) return {l.Spad_, l.S_, l.C_};
+  return {l.Spad_, l.S_,  l.C_, l.kh_, l.kw_, l.ph_,  // strides in the view
+          l.pw_,   l.H_,  l.W_, l.OW_, l.sh_, l.sw_};
 }
 
 void ConvolutionLayer::Forward_gpu(const std::vector<Blob*>& bottom,
@@ -112,52 +110,28 @@ void ConvolutionLayer::Forward_gpu(const std::vector<Blob*>& bottom,
   Engine& E = Engine::get();
   const int K = C_ / group_ * kh_ * kw_;
   const long NS = (long)N_ * Spad_;
-  Workspace& ws = Workspace::get_global();
   const float* x = bottom[0]->gpu_data();
   const float* w = blobs_[0]->gpu_data();
+  const float* bias = bias_ ? blobs_[1]->gpu_data() : nullptr;
   float* y = top[0]->mutable_gpu_data();
 
-  GemmEpi epi;
-  epi.spad = Spad_;
-  epi.S = S_;
-  epi.n_stride = (long)Cout_ * S_;
-  epi.bias = bias_ ? blobs_[1]->gpu_data() : nullptr;
+  // B is x through the plan's view, or the col buffer (cached for backward)
+  const bool col = xop_ == kExplicitCol;
+  const GemmView xv = conv_x_view(*this);
+  const float* b = x;
+  if (col) {
+    b = (float*)col_.reserve(sizeof(float) * (size_t)C_ * kh_ * kw_ * NS);
+    gpu::im2col_batched(E.stream, x, N_, C_, H_, W_, kh_, kw_, ph_, pw_, sh_,
+                        sw_, dh_, dw_, OH_, OW_, Spad_, (float*)col_.p);
+  }
+  GemmEpi epi = nchw_scatter(Spad_, S_, Cout_);
   epi.relu = fuse_relu_;
-  if (conv_is_1x1(*this)) {
-    GemmView xv{Spad_, S_, C_};  // plain NCHW view
-    gpu::gemm(E.stream, false, false, Cout_, NS, K, 1.f, w, K, x, 0, 0.f, y,
-              S_, &epi, nullptr, &xv);
-    return;
-  }
-  if (conv_implicit(*this)) {  // implicit im2col view (strides in-view)
-    GemmView xv{Spad_, S_, C_, kh_, kw_, ph_, pw_, H_, W_, OW_, sh_, sw_};
-    for (int g = 0; g < group_; ++g) {
-      epi.bias = bias_ ? blobs_[1]->gpu_data() + (long)g * (Cout_ / group_)
-                       : nullptr;
-      gpu::gemm(E.stream, false, false, Cout_ / group_, NS, K, 1.f,
-                w + (long)g * (Cout_ / group_) * K, K,
-                x + (long)g * (C_ / group_) * H_ * W_, 0, 0.f,
-                y + (long)g * (Cout_ / group_) * S_, S_, &epi, nullptr,
-                &xv);
-    }
-    return;
-  }
-  // strided: explicit col (cached for backward)
-  if (col_slot_ < 0) {
-    static int next_slot = 100;
-    col_slot_ = next_slot++;
-  }
-  float* colb =
-      (float*)ws.get(col_slot_, sizeof(float) * (size_t)C_ * kh_ * kw_ * NS);
-  gpu::im2col_batched(E.stream, x, N_, C_, H_, W_, kh_, kw_, ph_, pw_, sh_,
-                      sw_, dh_, dw_, OH_, OW_, Spad_, colb);
+  const ConvGroup o = conv_group(*this, NS);
   for (int g = 0; g < group_; ++g) {
-    epi.bias = bias_ ? blobs_[1]->gpu_data() + (long)g * (Cout_ / group_)
-                     : nullptr;
+    epi.bias = bias ? bias + g * o.bias : nullptr;
     gpu::gemm(E.stream, false, false, Cout_ / group_, NS, K, 1.f,
-              w + (long)g * (Cout_ / group_) * K, K,
-              colb + (long)g * K * NS, NS, 0.f,
-              y + (long)g * (Cout_ / group_) * S_, S_, &epi);
+              w + g * o.w, K, b + g * (col ? o.col : o.x), col ? NS : 0, 0.f,
+              y + g * o.y, S_, &epi, nullptr, col ? nullptr : &xv);
   }
 }
 
@@ -177,104 +151,80 @@ void ConvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
     gpu::bias_grad(E.stream, dy, N_, Cout_, S_,
                    blobs_[1]->mutable_gpu_diff());
 
-  if (conv_is_1x1(*this)) {
-    GemmView xv{Spad_, S_, C_};
-    gpu::gemm(E.stream, false, true, Cout_, K, NS, 1.f, dy, 0, x, 0, 0.f,
-              blobs_[0]->mutable_gpu_diff(), K, nullptr, &dyv, &xv);
-    if (prop_down[0]) {
-      GemmEpi epi;
-      epi.spad = Spad_;
-      epi.S = S_;
-      epi.n_stride = (long)C_ * S_;
-      gpu::gemm(E.stream, true, false, K, NS, Cout_, 1.f, w, K, dy, 0, 0.f,
-                bottom[0]->mutable_gpu_diff(), S_, &epi, nullptr, &dyv);
-    }
-    return;
-  }
-
-  if (conv_implicit(*this)) {
-    // wgrad: dW = dY-view · (implicit col of x)ᵀ — strides live in the view
-    GemmView xv{Spad_, S_, C_, kh_, kw_, ph_, pw_, H_, W_, OW_, sh_, sw_};
-    for (int g = 0; g < group_; ++g)
-      gpu::gemm(E.stream, false, true, Cout_ / group_, K, NS, 1.f,
-                dy + (long)g * (Cout_ / group_) * S_, 0,
-                x + (long)g * (C_ / group_) * H_ * W_, 0, 0.f,
-                blobs_[0]->mutable_gpu_diff() +
-                    (long)g * (Cout_ / group_) * K,
-                K, nullptr, &dyv, &xv);
-    if (prop_down[0]) {
-      if (conv_s1d1(*this)) {
-        // dgrad = forward conv of dY with flipped/transposed weights:
-        // dx[ci] = Σ_{co,ki,kj} dy[co][h-ki+ (kh-1-ph) ...] · Wt
-        float* wt =
-            (float*)ws.get(11, sizeof(float) * blobs_[0]->count());
-        gpu::weight_flip_grouped(E.stream, w, Cout_, C_ / group_, kh_, kw_,
-                                 group_, wt);
-        const long S_in = (long)H_ * W_;
-        const long spad_in = (S_in + 15) / 16 * 16;
-        const long NSin = (long)N_ * spad_in;
-        const int Kd = Cout_ / group_ * kh_ * kw_;
-        GemmEpi epi;
-        epi.spad = spad_in;
-        epi.S = S_in;
-        epi.n_stride = (long)C_ * S_in;
-        // dY viewed with the transposed-conv geometry: input dims (OH,OW),
-        // pad (k-1-p), output dims (H,W)
-        GemmView dyc{spad_in, S_in, Cout_, kh_, kw_, kh_ - 1 - ph_,
-                     kw_ - 1 - pw_, OH_, OW_, W_};
-        for (int g = 0; g < group_; ++g)
-          gpu::gemm(E.stream, false, false, C_ / group_, NSin, Kd, 1.f,
-                    wt + (long)g * (C_ / group_) * Kd, Kd,
-                    dy + (long)g * (Cout_ / group_) * S_, 0, 0.f,
-                    bottom[0]->mutable_gpu_diff() +
-                        (long)g * (C_ / group_) * S_in,
-                    S_in, &epi, nullptr, &dyc);
-      } else if (conv_scatter_dgrad(*this)) {
-        scatter_dgrad(top, bottom);
-      } else {
-        // strided kh>1 (conv1-style — only reached when prop_down, which
-        // the first layer never is): dcol = Wᵀ·dY, then gather col2im
-        float* dcol =
-            (float*)ws.get(1, sizeof(float) * (size_t)C_ * kh_ * kw_ * NS);
-        for (int g = 0; g < group_; ++g)
-          gpu::gemm(E.stream, true, false, K, NS, Cout_ / group_, 1.f,
-                    w + (long)g * (Cout_ / group_) * K, K,
-                    dy + (long)g * (Cout_ / group_) * S_, 0, 0.f,
-                    dcol + (long)g * K * NS, NS, nullptr, nullptr, &dyv);
-        gpu::col2im_batched(E.stream, dcol, N_, C_, H_, W_, kh_, kw_, ph_,
-                            pw_, sh_, sw_, dh_, dw_, OH_, OW_, Spad_,
-                            bottom[0]->mutable_gpu_diff());
-      }
-    }
-    return;
-  }
-
-  // strided: explicit col cached from this iteration's forward
-  CHECK_GE_(col_slot_, 0) << "conv backward before forward";
-  float* colb =
-      (float*)ws.get(col_slot_, sizeof(float) * (size_t)C_ * kh_ * kw_ * NS);
+  // wgrad: dW = dY-view · Bᵀ, B as in forward (the col buffer is the one
+  // this iteration's forward filled)
+  const bool col = xop_ == kExplicitCol;
+  const size_t colbytes = sizeof(float) * (size_t)C_ * kh_ * kw_ * NS;
+  CHECK_(!col || col_.bytes >= colbytes) << "conv backward before forward";
+  const GemmView xv = conv_x_view(*this);
+  const float* b = col ? (const float*)col_.p : x;
+  float* dw = blobs_[0]->mutable_gpu_diff();
+  const ConvGroup o = conv_group(*this, NS);
   for (int g = 0; g < group_; ++g)
     gpu::gemm(E.stream, false, true, Cout_ / group_, K, NS, 1.f,
-              dy + (long)g * (Cout_ / group_) * S_, 0,
-              colb + (long)g * K * NS, NS, 0.f,
-              blobs_[0]->mutable_gpu_diff() +
-                  (long)g * (Cout_ / group_) * K,
-              K, nullptr, &dyv);
-  if (prop_down[0]) {
-    if (conv_scatter_dgrad(*this)) {  // strided 1x1: no dcol/col2im
-      scatter_dgrad(top, bottom);
-      return;
+              dy + g * o.y, 0, b + g * (col ? o.col : o.x), col ? NS : 0,
+              0.f, dw + g * o.w, K, nullptr, &dyv, col ? nullptr : &xv);
+  if (!prop_down[0]) return;
+
+  float* dx = bottom[0]->mutable_gpu_diff();
+  switch (dgrad_) {
+    case kTnScatter: {  // dx = Wᵀ·dY scattered to NCHW; group 1 by the plan
+      const GemmEpi epi = nchw_scatter(Spad_, S_, C_);
+      gpu::gemm(E.stream, true, false, K, NS, Cout_, 1.f, w, K, dy, 0, 0.f,
+                dx, S_, &epi, nullptr, &dyv);
+      break;
     }
-    float* dcol =
-        (float*)ws.get(1, sizeof(float) * (size_t)C_ * kh_ * kw_ * NS);
-    for (int g = 0; g < group_; ++g)
-      gpu::gemm(E.stream, true, false, K, NS, Cout_ / group_, 1.f,
-                w + (long)g * (Cout_ / group_) * K, K,
-                dy + (long)g * (Cout_ / group_) * S_, 0, 0.f,
-                dcol + (long)g * K * NS, NS, nullptr, nullptr, &dyv);
-    gpu::col2im_batched(E.stream, dcol, N_, C_, H_, W_, kh_, kw_, ph_, pw_,
-                        sh_, sw_, dh_, dw_, OH_, OW_, Spad_,
-                        bottom[0]->mutable_gpu_diff());
+    case kFlipConv: {
+      // dgrad = forward conv of dY with flipped/transposed weights:
+      // dx[ci] = Σ_{co,ki,kj} dy[co][h-ki+ (kh-1-ph) ...] · Wt
+      float* wt = (float*)ws.get(Workspace::kFlipW,
+                                 sizeof(float) * blobs_[0]->count());
+      gpu::weight_flip_grouped(E.stream, w, Cout_, C_ / group_, kh_, kw_,
+                               group_, wt);
+      const long S_in = (long)H_ * W_;
+      const long spad_in = (S_in + 15) / 16 * 16;
+      const int Kd = Cout_ / group_ * kh_ * kw_;
+      const GemmEpi epi = nchw_scatter(spad_in, S_in, C_);
+      // dY viewed with the transposed-conv geometry: input dims (OH,OW),
+      // pad (k-1-p), output dims (H,W)
+      GemmView dyc{spad_in, S_in, Cout_, kh_, kw_, kh_ - 1 - ph_,
+                   kw_ - 1 - pw_, OH_, OW_, W_};
+      for (int g = 0; g < group_; ++g)
+        gpu::gemm(E.stream, false, false, C_ / group_, N_ * spad_in, Kd, 1.f,
+                  wt + g * o.w, Kd, dy + g * o.y, 0, 0.f, dx + g * o.x, S_in,
+                  &epi, nullptr, &dyc);
+      break;
+    }
+    case kStridedScatter: {
+      // strided 1x1 (projection shortcuts): dgrad touches only the sampled
+      // input pixels — zero dx, then a GEMM whose epilogue scatters column
+      // (oh, ow) to input pixel (oh*sh, ow*sw).  No dcol, no col2im.
+      gpu::set_const(E.stream, bottom[0]->count(), 0.f, dx);
+      GemmEpi epi = nchw_scatter(Spad_, S_, C_);
+      epi.Srow = (long)H_ * W_;  // rows are input channels of H*W pixels
+      epi.n_stride = C_ * epi.Srow;
+      epi.OWo = OW_;
+      epi.osh = sh_;
+      epi.osw = sw_;
+      epi.Wd = W_;
+      for (int g = 0; g < group_; ++g)
+        gpu::gemm(E.stream, true, false, C_ / group_, NS, Cout_ / group_,
+                  1.f, w + g * o.w, K, dy + g * o.y, 0, 0.f, dx + g * o.x, 0,
+                  &epi, nullptr, &dyv);
+      break;
+    }
+    case kCol2im: {
+      // dcol = Wᵀ·dY, then gather col2im (a strided im2col-view conv gets
+      // here only when prop_down, which a first layer never is)
+      float* dcol = (float*)ws.get(Workspace::kDcol, colbytes);
+      for (int g = 0; g < group_; ++g)
+        gpu::gemm(E.stream, true, false, K, NS, Cout_ / group_, 1.f,
+                  w + g * o.w, K, dy + g * o.y, 0, 0.f, dcol + g * o.col, NS,
+                  nullptr, nullptr, &dyv);
+      gpu::col2im_batched(E.stream, dcol, N_, C_, H_, W_, kh_, kw_, ph_, pw_,
+                          sh_, sw_, dh_, dw_, OH_, OW_, Spad_, dx);
+      break;
+    }
   }
 }
 
@@ -401,21 +351,30 @@ void BatchNormLayer::Backward_gpu(const std::vector<Blob*>& top,
   gpu::bn_bwd_stats(E.stream, x, dy, mean_.gpu_data(), inv_std_.gpu_data(),
                     N, C_, S, nb, sc_p, bi_p, fuse_relu_ ? 1 : 0, parts);
   gpu::bn_bwd_finalize(
-      E.stream, parts, nb, C_, (long)N * S,
-      scale_bias_ ? blobs_[3]->gpu_data() : nullptr, scale_bias_,
+      E.stream, parts, nb, C_, (long)N * S, sc_p, scale_bias_,
       scale_bias_ ? blobs_[3]->mutable_gpu_diff() : nullptr,
       scale_bias_ ? blobs_[4]->mutable_gpu_diff() : nullptr,
       m_dy_.mutable_gpu_data(), m_dyxn_.mutable_gpu_data());
   if (prop_down[0])
     gpu::bn_bwd_apply(E.stream, x, dy, mean_.gpu_data(),
-                      inv_std_.gpu_data(),
-                      scale_bias_ ? blobs_[3]->gpu_data() : nullptr,
-                      scale_bias_, m_dy_.gpu_data(), m_dyxn_.gpu_data(), N,
-                      C_, S, bi_p, fuse_relu_ ? 1 : 0,
-                      bottom[0]->mutable_gpu_diff());
+                      inv_std_.gpu_data(), sc_p, scale_bias_,
+                      m_dy_.gpu_data(), m_dyxn_.gpu_data(), N, C_, S, bi_p,
+                      fuse_relu_ ? 1 : 0, bottom[0]->mutable_gpu_diff());
 }
 
 // ----------------------------------------------------------------- Scale
+// Scale's and Bias's GPU constants + scratch, [zeros C][ones C][scratch 2C]
+// (the scratch starts as ones too), filled when C changes
+static float* zeros_ones(Blob& zo, int C) {
+  if (zo.count() != 4 * C) {
+    hipStream_t s = Engine::get().stream;
+    zo.Reshape({4 * C});
+    gpu::set_const(s, C, 0.f, zo.mutable_gpu_data());
+    gpu::set_const(s, 3L * C, 1.f, zo.mutable_gpu_data() + C);
+  }
+  return zo.mutable_gpu_data();
+}
+
 void ScaleLayer::Forward_gpu(const std::vector<Blob*>& bottom,
                              const std::vector<Blob*>& top) {
   Engine& E = Engine::get();
@@ -442,16 +401,11 @@ void ScaleLayer::Backward_gpu(const std::vector<Blob*>& top,
   const float* dy = top[0]->gpu_diff();
   // per-channel {sum dy, sum dy*x} via the BN bwd-stats reduction with
   // mean 0 / inv_std 1 (xn == x there); finalize writes dscale/dbias and
-  // scratch means we ignore.  zo_ layout: [zeros C][ones C][scratch 2C]
-  if (zo_.count() != 4 * C_) {
-    zo_.Reshape({4 * C_});
-    gpu::set_const(E.stream, C_, 0.f, zo_.mutable_gpu_data());
-    gpu::set_const(E.stream, 3L * C_, 1.f, zo_.mutable_gpu_data() + C_);
-  }
+  // scratch means we ignore.
+  float* zo = zeros_ones(zo_, C_);
   const int nb = gpu::bn_blocks_per_channel(N, C_);
   partials_.Reshape({(int)(C_ * nb * 4)});
   void* parts = partials_.mutable_gpu_data();
-  float* zo = zo_.mutable_gpu_data();
   gpu::bn_bwd_stats(E.stream, x, dy, /*mean=*/zo, /*inv_std=*/zo + C_, N,
                     C_, S, nb, nullptr, nullptr, 0, parts);
   gpu::bn_bwd_finalize(E.stream, parts, nb, C_, (long)N * S,
@@ -470,15 +424,10 @@ void BiasLayer::Forward_gpu(const std::vector<Blob*>& bottom,
   Engine& E = Engine::get();
   const int N = bottom[0]->num();
   const long S = bottom[0]->count() / ((long)N * C_);
-  // y = x*1 + b[c]: the ones live in zo_ ([zeros C][ones C][scratch 2C])
-  if (zo_.count() != 4 * C_) {
-    zo_.Reshape({4 * C_});
-    gpu::set_const(E.stream, C_, 0.f, zo_.mutable_gpu_data());
-    gpu::set_const(E.stream, 3L * C_, 1.f, zo_.mutable_gpu_data() + C_);
-  }
-  gpu::chan_affine(E.stream, bottom[0]->gpu_data(),
-                   zo_.mutable_gpu_data() + C_, blobs_[0]->gpu_data(), N,
-                   C_, S, top[0]->mutable_gpu_data());
+  // y = x*1 + b[c]: the ones live in zo_
+  gpu::chan_affine(E.stream, bottom[0]->gpu_data(), zeros_ones(zo_, C_) + C_,
+                   blobs_[0]->gpu_data(), N, C_, S,
+                   top[0]->mutable_gpu_data());
 }
 
 void BiasLayer::Backward_gpu(const std::vector<Blob*>& top,

@@ -147,9 +147,9 @@ struct GemmEpi {
 // With kh > 0 the view becomes an IMPLICIT-IM2COL view (the north_star's
 // implicit-GEMM conv): r indexes a col row (c, ki, kj), sp an output pixel
 // (oh, ow); the element is x[n][c][oh*sh-ph+ki][ow*sw-pw+kj] (0 outside) —
-// the col matrix is never materialized.  stride/dilation 1 only (every
-// ResNet/GoogLeNet/AlexNet conv that needs backward-data is s1/d1; strided
-// convs use the explicit col path).
+// the col matrix is never materialized.  Strides live in the view (sh, sw);
+// dilation is 1 only — dilated convs use the explicit col path.  Which
+// convs take a view is the conv plan's decision (layers_gpu.cpp).
 struct GemmView {
   long spad = 0;  // 0 = plain operand
   long S = 0;     // valid pixels per image (OH*OW)

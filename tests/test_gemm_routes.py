@@ -42,8 +42,8 @@ def route_key(r):
     return tuple(sorted(r.items()))
 
 
-# conv cases: N, C, H, W -> Co, k / s / p / group.  Routes in the order
-# forward, wgrad, dgrad.
+# conv cases: N, C, H, W -> Co, k / s / p / group / dilation.  Routes in the
+# order forward, wgrad, dgrad.
 CONV_CASES = {
     # 1x1: fwd/dgrad on the 64-row slim tile through the channel view (NN
     # and TN) with the NCHW scatter; wgrad NT, both operands channel views,
@@ -191,6 +191,57 @@ CONV_CASES = {
         "bv=im2col epi=none",
         "fam=f32_128 ta=0 tb=0 sk=1 M=200 N=288 K=1872 tm=2 tn=3 bv=im2col "
         "epi=scatter",
+    ]),
+    # group 2 on the explicit col (OW < 24): forward and wgrad read the
+    # group's K rows of the cached col buffer, dgrad writes the group's rows
+    # of dcol before the one col2im.  M = Cout/group = 8.
+    "H3": (dict(N=2, C=16, H=7, W=13, Co=16, k=3, s=1, p=1, grp=2), [
+        "fam=slim32 ta=0 tb=0 sk=1 M=8 N=192 K=72 tm=1 tn=1 epi=scatter "
+        "bias=row",
+        "fam=slim32 ta=0 tb=1 sk=2 M=8 N=72 K=192 tm=1 tn=1 av=chan "
+        "epi=none",
+        "fam=f32_128 ta=1 tb=0 sk=1 M=72 N=192 K=8 tm=1 tn=2 bv=chan "
+        "epi=none",
+    ]),
+    # group 2 on the strided 1x1: explicit col forward / wgrad (N = 8 keeps
+    # wgrad on the 128-tile with 4 K-waves), per-group strided-scatter dgrad
+    "H4": (dict(N=3, C=16, H=9, W=11, Co=16, k=1, s=2, p=0, grp=2), [
+        "fam=slim32 ta=0 tb=0 sk=1 M=8 N=96 K=8 tm=1 tn=1 epi=scatter "
+        "bias=row",
+        "fam=f32_128 ta=0 tb=1 sk=1 kw=4 M=8 N=8 K=96 tm=1 tn=1 av=chan "
+        "epi=none",
+        "fam=slim32 ta=1 tb=0 sk=1 M=8 N=96 K=8 tm=1 tn=1 bv=chan "
+        "epi=sscatter",
+    ]),
+    # group 2 on the 1x1/s1: not the single-call 1x1 (group > 1), so the
+    # im2col view with kh = 1 and the flipped-weight dgrad
+    "H5": (dict(N=2, C=16, H=5, W=27, Co=16, k=1, s=1, p=0, grp=2), [
+        "fam=slim32 ta=0 tb=0 sk=1 M=8 N=288 K=8 tm=1 tn=2 bv=im2col "
+        "epi=scatter bias=row",
+        "fam=f32_128 ta=0 tb=1 sk=3 kw=4 M=8 N=8 K=288 tm=1 tn=1 av=chan "
+        "bv=im2col epi=none",
+        "fam=slim32 ta=0 tb=0 sk=1 M=8 N=288 K=8 tm=1 tn=2 bv=im2col "
+        "epi=scatter",
+    ]),
+    # 1x1 with pad 1 (output 7x29): im2col view with kh = 1; the dgrad view
+    # of dY has pad kh-1-ph = -1
+    "P1": (dict(N=2, C=8, H=5, W=27, Co=16, k=1, s=1, p=1), [
+        "fam=slim32 ta=0 tb=0 sk=1 M=16 N=416 K=8 tm=1 tn=2 bv=im2col "
+        "epi=scatter bias=row",
+        "fam=f32_128 ta=0 tb=1 sk=4 kw=4 M=16 N=8 K=416 tm=1 tn=1 av=chan "
+        "bv=im2col epi=none",
+        "fam=slim32 ta=0 tb=0 sk=1 M=8 N=288 K=16 tm=1 tn=2 bv=im2col "
+        "epi=scatter",
+    ]),
+    # dilation 2 (always the explicit col): S32's GEMMs between a dilated
+    # im2col and col2im
+    "DIL": (dict(N=2, C=8, H=13, W=13, Co=16, k=3, s=1, p=2, d=2), [
+        "fam=slim32 ta=0 tb=0 sk=1 M=16 N=352 K=72 tm=1 tn=2 epi=scatter "
+        "bias=row",
+        "fam=slim32 ta=0 tb=1 sk=3 M=16 N=72 K=352 tm=1 tn=1 av=chan "
+        "epi=none",
+        "fam=f32_128 ta=1 tb=0 sk=1 M=72 N=352 K=16 tm=1 tn=3 bv=chan "
+        "epi=none",
     ]),
     # the class every older per-layer conv check sits in (Cout <= 16):
     # the 32-row slim tile, with and without split-K
@@ -460,10 +511,10 @@ def _step(shape, body):
     net.backward()
 
 
-def _conv_step(N, C, H, W, Co, k, s, p, grp=1, relu=False):
+def _conv_step(N, C, H, W, Co, k, s, p, grp=1, d=1, relu=False):
     body = f"""layer {{ name: "conv" type: "Convolution" bottom: "in0"
   top: "out" convolution_param {{ num_output: {Co} kernel_size: {k}
-  stride: {s} pad: {p} group: {grp} }} }}"""
+  stride: {s} pad: {p} group: {grp} dilation: {d} }} }}"""
     if relu:
         body += '\nlayer { name: "r" type: "ReLU" bottom: "out" top: "out" }'
     _step((N, C, H, W), body)
