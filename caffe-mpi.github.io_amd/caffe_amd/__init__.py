@@ -43,7 +43,27 @@ _lib.caffe_comm_init.argtypes = [_vp, ctypes.c_int, ctypes.c_int,
 _lib.caffe_comm_bcast_weights.argtypes = [_vp]
 _lib.caffe_net_create.argtypes = [ctypes.c_char_p, ctypes.c_int,
                                   ctypes.c_int]
+_lib.caffe_net_create_state.argtypes = [ctypes.c_char_p, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_char_p,
+                                        ctypes.c_int]
+_lib.caffe_net_create_state.restype = ctypes.c_void_p
+_lib.caffe_solver_num_test_nets.argtypes = [_vp]
+_lib.caffe_solver_test_net.argtypes = [_vp, ctypes.c_int]
+_lib.caffe_solver_test_net.restype = ctypes.c_void_p
+_lib.caffe_solver_test.argtypes = [_vp, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_char_p, ctypes.c_int,
+                                   ctypes.POINTER(ctypes.c_float),
+                                   ctypes.c_int]
 _lib.caffe_net_free.argtypes = [_vp]
+_lib.caffe_net_num_layers.argtypes = [_vp]
+_lib.caffe_net_blob_names.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
+_lib.caffe_net_layer_info.argtypes = [_vp, ctypes.c_int, ctypes.c_char_p,
+                                      ctypes.c_int, ctypes.c_char_p,
+                                      ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_int)]
+_lib.caffe_net_blob_cpu_ptr.restype = ctypes.POINTER(ctypes.c_float)
+_lib.caffe_net_blob_cpu_ptr.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int,
+                                        ctypes.c_int]
 _lib.caffe_net_forward.argtypes = [_vp]
 _lib.caffe_net_backward.argtypes = [_vp]
 _lib.caffe_net_loss.argtypes = [_vp]
@@ -245,8 +265,16 @@ class Net:
         self._owned = owned
 
     @classmethod
-    def from_file(cls, path, phase=0, batch_override=0):
-        h = _ckp(_lib.caffe_net_create(path.encode(), phase, batch_override))
+    def from_file(cls, path, phase=0, batch_override=0, stages=(), level=0):
+        """stages / level: the NetState the layers' include / exclude rules
+        are matched against (stage, not_stage, min_level, max_level)."""
+        if not stages and level == 0:
+            h = _ckp(_lib.caffe_net_create(path.encode(), phase,
+                                           batch_override))
+        else:
+            h = _ckp(_lib.caffe_net_create_state(
+                path.encode(), phase, level, ",".join(stages).encode(),
+                batch_override))
         return cls(h, owned=True)
 
     def forward(self):
@@ -269,6 +297,22 @@ class Net:
         _ck(_lib.caffe_net_blob_shape(self._h, name.encode(), shape, 8,
                                       ctypes.byref(nd)))
         return tuple(shape[i] for i in range(nd.value))
+
+    def blob_names(self):
+        buf = ctypes.create_string_buffer(65536)
+        _ck(_lib.caffe_net_blob_names(self._h, buf, 65536))
+        return [s for s in buf.value.decode().split("\n") if s]
+
+    def layer_names(self):
+        nbuf = ctypes.create_string_buffer(256)
+        tbuf = ctypes.create_string_buffer(256)
+        nb = ctypes.c_int()
+        out = []
+        for i in range(_lib.caffe_net_num_layers(self._h)):
+            _ck(_lib.caffe_net_layer_info(self._h, i, nbuf, 256, tbuf, 256,
+                                          ctypes.byref(nb)))
+            out.append(nbuf.value.decode())
+        return out
 
     def blob(self, name, diff=False):
         shape = self.blob_shape(name)
@@ -332,6 +376,28 @@ class Solver:
 
     def step(self, iters=1):
         _ck(_lib.caffe_solver_step(self._h, iters))
+
+    @property
+    def test_nets(self):
+        """The solver's TEST nets (one per test_state of the solver file, or
+        one default TEST net), sharing the trained weights."""
+        n = _lib.caffe_solver_num_test_nets(self._h)
+        if n < 0:
+            raise CaffeError(_lib.caffe_last_error().decode())
+        return [Net(_ckp(_lib.caffe_solver_test_net(self._h, i)))
+                for i in range(n)]
+
+    def test(self, i, iters):
+        """Run test net i for `iters` batches from the start of its data:
+        {top blob name: averaged value} of every scored top."""
+        cap, rows = 4096, 64
+        names = ctypes.create_string_buffer(cap)
+        vals = (ctypes.c_float * rows)()
+        n = _lib.caffe_solver_test(self._h, i, iters, names, cap, vals, rows)
+        if n < 0:
+            raise CaffeError(_lib.caffe_last_error().decode())
+        keys = names.value.decode().split("\n") if n else []
+        return {k: vals[j] for j, k in enumerate(keys[:rows])}
 
     @property
     def iter(self):

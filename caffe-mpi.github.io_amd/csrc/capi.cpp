@@ -169,6 +169,40 @@ caffe_net_t caffe_solver_net(caffe_solver_t s) {
   return (caffe_net_t)&S(s)->net();
 }
 
+int caffe_solver_num_test_nets(caffe_solver_t s) {
+  API_TRY
+  return S(s)->num_test_nets();
+  API_CATCH
+}
+
+caffe_net_t caffe_solver_test_net(caffe_solver_t s, int i) {
+  API_TRY
+  Net* n = S(s)->test_net(i);
+  CHECK_(n) << "no test net " << i << " (the solver has "
+            << S(s)->num_test_nets() << ")";
+  return (caffe_net_t)n;
+  API_CATCH_NULL
+}
+
+int caffe_solver_test(caffe_solver_t s, int i, int iters, char* names_out,
+                      int name_cap, float* values_out, int max_scores) {
+  API_TRY
+  Net* n = S(s)->test_net(i);
+  CHECK_(n) << "no test net " << i << " (the solver has "
+            << S(s)->num_test_nets() << ")";
+  CHECK_GT_(iters, 0);
+  const auto scores = n->test_scores(iters);
+  std::string joined;
+  for (size_t k = 0; k < scores.size(); ++k) {
+    if (k) joined += "\n";
+    joined += scores[k].top;
+    if ((int)k < max_scores) values_out[k] = (float)scores[k].value;
+  }
+  if (name_cap > 0) snprintf(names_out, name_cap, "%s", joined.c_str());
+  return (int)scores.size();
+  API_CATCH
+}
+
 int caffe_solver_snapshot(caffe_solver_t s) {
   API_TRY
   S(s)->Snapshot();
@@ -257,6 +291,26 @@ caffe_net_t caffe_net_create(const char* path, int phase,
   API_TRY
   auto n = std::make_shared<Net>(parse_prototxt_file(path),
                                  phase ? Phase::TEST : Phase::TRAIN,
+                                 batch_override);
+  g_nets.push_back(n);
+  return (caffe_net_t)n.get();
+  API_CATCH_NULL
+}
+
+caffe_net_t caffe_net_create_state(const char* path, int phase, int level,
+                                   const char* stages, int batch_override) {
+  API_TRY
+  NetState st;
+  st.phase = phase ? Phase::TEST : Phase::TRAIN;
+  st.level = level;
+  const std::string list = stages ? stages : "";
+  for (size_t pos = 0; pos < list.size();) {
+    size_t next = list.find(',', pos);
+    if (next == std::string::npos) next = list.size();
+    if (next > pos) st.stages.push_back(list.substr(pos, next - pos));
+    pos = next + 1;
+  }
+  auto n = std::make_shared<Net>(parse_prototxt_file(path), st,
                                  batch_override);
   g_nets.push_back(n);
   return (caffe_net_t)n.get();

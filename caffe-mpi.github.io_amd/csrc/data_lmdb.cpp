@@ -307,8 +307,9 @@ void DataLayer::forward_lmdb_cpu(const std::vector<Blob*>& top) {
   LmdbFeed& F = *feed_;
   auto& slot = F.get(E.data_iter);
   F.transform_cpu(slot, top[0]->mutable_cpu_data());
-  memcpy(top[1]->mutable_cpu_data(), slot.labels.data(),
-         sizeof(float) * batch_);
+  if (top.size() > 1)
+    memcpy(top[1]->mutable_cpu_data(), slot.labels.data(),
+           sizeof(float) * batch_);
 }
 
 void DataLayer::forward_lmdb_gpu(const std::vector<Blob*>& top) {
@@ -353,9 +354,10 @@ void DataLayer::forward_lmdb_gpu(const std::vector<Blob*>& top) {
                                          : dmean          ? 1
                                                           : 0,
                     F.scale, top[0]->mutable_gpu_data());
-  HIP_CHECK(hipMemcpyAsync(top[1]->mutable_gpu_data(), F.pin_lab[p],
-                           sizeof(float) * batch_, hipMemcpyHostToDevice,
-                           E.stream));
+  if (top.size() > 1)
+    HIP_CHECK(hipMemcpyAsync(top[1]->mutable_gpu_data(), F.pin_lab[p],
+                             sizeof(float) * batch_, hipMemcpyHostToDevice,
+                             E.stream));
   HIP_CHECK(hipEventRecord(F.ev[p], E.stream));
 }
 

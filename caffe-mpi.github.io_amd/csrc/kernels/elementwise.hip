@@ -36,12 +36,14 @@ static inline int nblocks(long n, int per_thread = 1) {
 // launches, so the log cannot disagree with what ran.
 enum KOp {
   kPoolMaxFwd, kPoolMaxBwd, kPoolAveFwd, kPoolAveBwd, kBnFwdStats,
-  kBnBwdStats, kLrnFwd, kLrnBwd, kSoftmaxFwd, kSgdSeg, kSolverSeg
+  kBnBwdStats, kLrnFwd, kLrnBwd, kSoftmaxFwd, kSgdSeg, kSolverSeg,
+  kSigmoidFwd, kSigmoidBwd, kSigmoidCeFwd, kSigmoidCeBwd, kEuclidFwd,
+  kEuclidBwd
 };
 enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
             kVarScalar, kVarRing5 };
 struct KernelRec {
-  long a, b, c;  // per-op fields, see kernel_trace_read
+  long a, b, c, d;  // per-op fields, see kernel_trace_read
   unsigned char op, var;
 };
 constexpr size_t kKTraceCap = 4096;
@@ -49,16 +51,17 @@ static std::atomic<bool> g_ktrace_on{false};
 static std::mutex g_ktrace_mu;
 static std::vector<KernelRec> g_ktrace_log;
 
-static void ktrace_push(int op, int var, long a, long b, long c) {
+static void ktrace_push(int op, int var, long a, long b, long c,
+                        long d = 0) {
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   if (g_ktrace_log.size() < kKTraceCap)
     g_ktrace_log.push_back(
-        KernelRec{a, b, c, (unsigned char)op, (unsigned char)var});
+        KernelRec{a, b, c, d, (unsigned char)op, (unsigned char)var});
 }
 static inline void ktrace(int op, int var = kVarNone, long a = 0, long b = 0,
-                          long c = 0) {
+                          long c = 0, long d = 0) {
   if (g_ktrace_on.load(std::memory_order_relaxed))
-    ktrace_push(op, var, a, b, c);
+    ktrace_push(op, var, a, b, c, d);
 }
 void kernel_trace(bool enable) {
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
@@ -73,7 +76,9 @@ long kernel_trace_read(char* buf, long cap) {
   static const char* const op[] = {
       "pool_max_fwd", "pool_max_bwd", "pool_ave_fwd", "pool_ave_bwd",
       "bn_fwd_stats", "bn_bwd_stats", "lrn_fwd",      "lrn_bwd",
-      "softmax_fwd",  "sgd_seg",      "solver_seg"};
+      "softmax_fwd",  "sgd_seg",      "solver_seg",   "sigmoid_fwd",
+      "sigmoid_bwd",  "sigmoid_ce_fwd", "sigmoid_ce_bwd", "euclid_fwd",
+      "euclid_bwd"};
   // solver_seg keeps rule * 2 + l1 in the var byte
   static const char* const rule[] = {"sgd",     "nesterov", "adagrad",
                                      "rmsprop", "adadelta", "adam"};
@@ -114,6 +119,19 @@ long kernel_trace_read(char* buf, long cap) {
                      "op=%s rule=%s reg=%s lo=%ld hi=%ld nseg=%ld\n",
                      op[r.op], rule[r.var >> 1], (r.var & 1) ? "L1" : "L2",
                      r.a, r.b, r.c);
+        break;
+      case kSigmoidFwd:
+      case kSigmoidBwd:
+      case kSigmoidCeBwd:
+      case kEuclidBwd:
+        n = snprintf(line, sizeof(line), "op=%s n=%ld blocks=%ld passes=%ld\n",
+                     op[r.op], r.a, r.b, r.c);
+        break;
+      case kSigmoidCeFwd:
+      case kEuclidFwd:
+        n = snprintf(line, sizeof(line),
+                     "op=%s n=%ld blocks=%ld partials=%ld passes=%ld\n",
+                     op[r.op], r.a, r.b, r.c, r.d);
         break;
       default:
         n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld\n",
@@ -1404,6 +1422,201 @@ void softmaxloss_bwd(hipStream_t s, const float* prob, const float* label,
   PerfScope perf(PERF_CLASS("softmax"), s, 0, 8.0 * total);
   hipLaunchKernelGGL(k_sm_loss_bwd, dim3(nblocks(total, 4)), dim3(TPB), 0,
                      s, prob, label, outer, C, inner, scale, dx);
+}
+
+// ------------------------------------------- sigmoid, its loss, euclidean
+// Flat float4 streaming over n elements.  The pack at the edge is loaded
+// whole (allocations are padded to 16 floats) and its lanes past n are kept
+// out of every sum and every store: a blob reshaped smaller, or a top that
+// shares memory with a larger blob, has live values there.
+__device__ __forceinline__ void store_pack(float* __restrict__ y, long i,
+                                           long n, f4 v) {
+  if (4 * i + 4 <= n) {
+    ((f4*)y)[i] = v;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (4 * i + j < n) y[4 * i + j] = v[j];
+  }
+}
+// grid of a flat pack kernel and, for the trace, how many grid-stride
+// passes its busiest thread makes
+struct PackGrid {
+  long n4;
+  int blocks;
+  long passes;
+};
+static inline PackGrid pack_grid(long n) {
+  PackGrid g;
+  g.n4 = (n + 3) / 4;
+  g.blocks = std::max(1, nblocks(g.n4, 4));
+  const long threads = (long)g.blocks * TPB;
+  g.passes = (g.n4 + threads - 1) / threads;
+  return g;
+}
+
+// x and y may be the same buffer (in-place Sigmoid): no __restrict__
+__global__ void k_sigmoid_fwd(const f4* x, long n, float* y) {
+  VEC_GRID(i, (n + 3) / 4) {
+    f4 v = x[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = sigmoid_value(v[j]);
+    store_pack(y, i, n, v);
+  }
+}
+void sigmoid_fwd(hipStream_t s, const float* x, long n, float* y) {
+  PerfScope perf(PERF_CLASS("sigmoid"), s, 0, 8.0 * n);
+  const PackGrid g = pack_grid(n);
+  hipLaunchKernelGGL(k_sigmoid_fwd, dim3(g.blocks), dim3(TPB), 0, s,
+                     (const f4*)x, n, y);
+  ktrace(kSigmoidFwd, kVarNone, n, g.blocks, g.passes);
+}
+
+// dy and dx may be the same buffer (in-place Sigmoid)
+__global__ void k_sigmoid_bwd(const f4* __restrict__ y, const f4* dy, long n,
+                              float* dx) {
+  VEC_GRID(i, (n + 3) / 4) {
+    const f4 v = y[i];
+    f4 d = dy[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) d[j] *= v[j] * (1.f - v[j]);
+    store_pack(dx, i, n, d);
+  }
+}
+void sigmoid_bwd(hipStream_t s, const float* y, const float* dy, long n,
+                 float* dx) {
+  PerfScope perf(PERF_CLASS("sigmoid"), s, 0, 12.0 * n);
+  const PackGrid g = pack_grid(n);
+  hipLaunchKernelGGL(k_sigmoid_bwd, dim3(g.blocks), dim3(TPB), 0, s,
+                     (const f4*)y, (const f4*)dy, n, dx);
+  ktrace(kSigmoidBwd, kVarNone, n, g.blocks, g.passes);
+}
+
+// Loss sums, two-stage and deterministic: every thread adds Term(a, b) of
+// its packs into one double, the block tree-reduces them in a fixed order
+// and stores partials[blockIdx.x]; k_loss_final then adds the partials, again
+// in a fixed order, and writes the scaled float.  Same grid for the same n,
+// so two forwards of one input agree bit for bit.
+struct SigmoidCeTerm {
+  __device__ __forceinline__ float operator()(float x, float t) const {
+    return sigmoid_ce_term(x, t);
+  }
+};
+struct EuclidTerm {
+  __device__ __forceinline__ float operator()(float a, float b) const {
+    const float d = a - b;
+    return d * d;
+  }
+};
+__device__ __forceinline__ double block_sum(double acc) {
+  __shared__ double sh[TPB];
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = TPB / 2; off > 0; off >>= 1) {
+    if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+    __syncthreads();
+  }
+  return sh[0];
+}
+template <typename Term>
+__device__ __forceinline__ void loss_partial(const f4* __restrict__ a,
+                                             const f4* __restrict__ b, long n,
+                                             double* __restrict__ partials) {
+  const Term term;
+  double acc = 0;
+  VEC_GRID(i, (n + 3) / 4) {
+    const f4 va = a[i];
+    const f4 vb = b[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (4 * i + j < n) acc += (double)term(va[j], vb[j]);
+  }
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+__global__ void k_sigmoid_ce_fwd(const f4* __restrict__ x,
+                                 const f4* __restrict__ t, long n,
+                                 double* __restrict__ partials) {
+  loss_partial<SigmoidCeTerm>(x, t, n, partials);
+}
+__global__ void k_euclid_fwd(const f4* __restrict__ a,
+                             const f4* __restrict__ b, long n,
+                             double* __restrict__ partials) {
+  loss_partial<EuclidTerm>(a, b, n, partials);
+}
+// one block: thread k adds partials k, k + TPB, ... then the tree
+__global__ void k_loss_final(const double* __restrict__ partials, int np,
+                             double scale, float* __restrict__ loss) {
+  double acc = 0;
+  for (int i = threadIdx.x; i < np; i += TPB) acc += partials[i];
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0) loss[0] = (float)(sum * scale);
+}
+int loss_partials(long n) { return pack_grid(n).blocks; }
+
+template <typename K>
+static void loss_fwd_launch(K kernel, int op, hipStream_t s, const float* a,
+                            const float* b, long n, double scale,
+                            double* partials, float* loss_out) {
+  PerfScope perf(PERF_CLASS("loss"), s, 0, 8.0 * n);
+  const PackGrid g = pack_grid(n);
+  hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(TPB), 0, s, (const f4*)a,
+                     (const f4*)b, n, partials);
+  hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(TPB), 0, s,
+                     (const double*)partials, g.blocks, scale, loss_out);
+  ktrace(op, kVarNone, n, g.blocks, g.blocks, g.passes);
+}
+void sigmoid_ce_fwd(hipStream_t s, const float* x, const float* t, long n,
+                    int num, double* partials, float* loss_out) {
+  loss_fwd_launch(k_sigmoid_ce_fwd, kSigmoidCeFwd, s, x, t, n, 1.0 / num,
+                  partials, loss_out);
+}
+void euclid_fwd(hipStream_t s, const float* a, const float* b, long n,
+                int num, double* partials, float* loss_out) {
+  loss_fwd_launch(k_euclid_fwd, kEuclidFwd, s, a, b, n, 0.5 / num, partials,
+                  loss_out);
+}
+
+__global__ void k_sigmoid_ce_bwd(const f4* __restrict__ x,
+                                 const f4* __restrict__ t, long n,
+                                 float scale, float* __restrict__ dx) {
+  VEC_GRID(i, (n + 3) / 4) {
+    f4 v = x[i];
+    const f4 tv = t[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (sigmoid_value(v[j]) - tv[j]) * scale;
+    store_pack(dx, i, n, v);
+  }
+}
+void sigmoid_ce_bwd(hipStream_t s, const float* x, const float* t, long n,
+                    float scale, float* dx) {
+  PerfScope perf(PERF_CLASS("loss"), s, 0, 12.0 * n);
+  const PackGrid g = pack_grid(n);
+  hipLaunchKernelGGL(k_sigmoid_ce_bwd, dim3(g.blocks), dim3(TPB), 0, s,
+                     (const f4*)x, (const f4*)t, n, scale, dx);
+  ktrace(kSigmoidCeBwd, kVarNone, n, g.blocks, g.passes);
+}
+
+// da / db null = that bottom takes no gradient; a zero scale still writes
+// (zeros): the split above the bottom sums this diff
+__global__ void k_euclid_bwd(const f4* __restrict__ a,
+                             const f4* __restrict__ b, long n, float scale_a,
+                             float* __restrict__ da, float scale_b,
+                             float* __restrict__ db) {
+  VEC_GRID(i, (n + 3) / 4) {
+    const f4 d = a[i] - b[i];
+    if (da) store_pack(da, i, n, d * scale_a);
+    if (db) store_pack(db, i, n, d * scale_b);
+  }
+}
+void euclid_bwd(hipStream_t s, const float* a, const float* b, long n,
+                float scale_a, float* da, float scale_b, float* db) {
+  PerfScope perf(PERF_CLASS("loss"), s, 0,
+                 (8.0 + (da ? 4.0 : 0.0) + (db ? 4.0 : 0.0)) * n);
+  const PackGrid g = pack_grid(n);
+  hipLaunchKernelGGL(k_euclid_bwd, dim3(g.blocks), dim3(TPB), 0, s,
+                     (const f4*)a, (const f4*)b, n, scale_a, da, scale_b, db);
+  ktrace(kEuclidBwd, kVarNone, n, g.blocks, g.passes);
 }
 
 // ------------------------------------------------------- row/col sums

@@ -98,6 +98,9 @@ class Layer {
     loss_[i] = v;
   }
   virtual float default_loss_weight() const { return 0.f; }
+  // a loss layer's tops start no gradient of their own under force_backward
+  // (reference LossLayer: the top is a scalar whose diff is the loss weight)
+  virtual bool is_loss_layer() const { return false; }
 
  protected:
   PMsgPtr param_;
@@ -141,6 +144,7 @@ struct Workspace {
     kSplitK,    // gemm(): split-K partial slabs
     kFlipW,     // conv dgrad: flipped/transposed weights
     kBiasPart,  // bias_grad(): per-slice double partials
+    kLossPart,  // sigmoid_ce_fwd() / euclid_fwd(): per-block double partials
     kNumSlots
   };
   void* get(Slot slot, size_t bytes);  // device (GPU mode) / host (CPU mode)
@@ -175,7 +179,8 @@ class DataLayer : public Layer {  // synthetic or LMDB source (§8a a12,
                     const std::vector<Blob*>&) override {}
   void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
                     const std::vector<Blob*>&) override {}
-  int min_top_blobs() const override { return 2; }
+  // one top: data only, no label is produced (the autoencoder's Data layers)
+  int min_top_blobs() const override { return 1; }
   int max_top_blobs() const override { return 2; }
   int min_bottom_blobs() const override { return 0; }
   int max_bottom_blobs() const override { return 0; }
@@ -527,8 +532,88 @@ class SoftmaxWithLossLayer : public Layer {
   void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
                     const std::vector<Blob*>&) override;
   float default_loss_weight() const override { return 1.f; }
+  bool is_loss_layer() const override { return true; }
   int outer_ = 0, C_ = 0, inner_ = 0;
   Blob prob_;
+};
+
+// Sigmoid (reference layers/sigmoid_layer.cpp/.cu): y = 1 / (1 + exp(-x)),
+// in-place legal — backward reads the top data only
+class SigmoidLayer : public Layer {
+ public:
+  using Layer::Layer;
+  void Reshape(const std::vector<Blob*>& b,
+               const std::vector<Blob*>& t) override {
+    if (b[0] != t[0]) t[0]->ReshapeLike(*b[0]);
+  }
+  void Forward_cpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Forward_gpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Backward_cpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+};
+
+// SigmoidCrossEntropyLoss (reference
+// layers/sigmoid_cross_entropy_loss_layer.cpp): the stable per-element form
+// summed and divided by num.  σ(x) is not kept; backward recomputes it.
+class SigmoidCrossEntropyLossLayer : public Layer {
+ public:
+  using Layer::Layer;
+  int min_bottom_blobs() const override { return 2; }
+  int max_bottom_blobs() const override { return 2; }
+  void LayerSetUp(const std::vector<Blob*>&,
+                  const std::vector<Blob*>&) override;
+  void Reshape(const std::vector<Blob*>&, const std::vector<Blob*>&) override;
+  void Forward_cpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Forward_gpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Backward_cpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  float default_loss_weight() const override { return 1.f; }
+  bool is_loss_layer() const override { return true; }
+};
+
+// EuclideanLoss (reference layers/euclidean_loss_layer.cpp):
+// Σ (a - b)² / num / 2; a - b is recomputed in backward, never stored
+class EuclideanLossLayer : public Layer {
+ public:
+  using Layer::Layer;
+  int min_bottom_blobs() const override { return 2; }
+  int max_bottom_blobs() const override { return 2; }
+  void Reshape(const std::vector<Blob*>&, const std::vector<Blob*>&) override;
+  void Forward_cpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Forward_gpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Backward_cpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  float default_loss_weight() const override { return 1.f; }
+  bool is_loss_layer() const override { return true; }
+};
+
+// Flatten (reference layers/flatten_layer.cpp): axes [axis, end_axis]
+// collapse into one; the top shares the bottom's data and diff memory, so
+// neither direction runs a kernel or a copy
+class FlattenLayer : public Layer {
+ public:
+  using Layer::Layer;
+  void Reshape(const std::vector<Blob*>&, const std::vector<Blob*>&) override;
+  void Forward_cpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override {}
+  void Forward_gpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override {}
+  void Backward_cpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override {}
+  void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override {}
 };
 
 class AccuracyLayer : public Layer {  // CPU-resident (reference: CPU only)

@@ -65,6 +65,13 @@ void fill_blob(Blob& b, const PMsgPtr& filler, std::mt19937_64& rng) {
                                   : "constant";
   float* p = b.mutable_cpu_data();
   const long n = b.count();
+  // sparse (filler.hpp:109-125): the gaussian filler alone takes it; absent
+  // means -1, and then no extra RNG draw happens
+  const long sparse = filler ? filler->inum("sparse", -1) : -1;
+  CHECK_GE_(sparse, -1L) << "filler sparse: " << sparse;
+  if (sparse >= 0 && type != "gaussian")
+    CAMD_FATAL << "Sparsity not supported by this Filler (" << type
+               << "): only gaussian takes sparse";
   if (type == "constant") {
     const float v = filler ? (float)filler->num("value", 0) : 0.f;
     for (long i = 0; i < n; ++i) p[i] = v;
@@ -76,6 +83,16 @@ void fill_blob(Blob& b, const PMsgPtr& filler, std::mt19937_64& rng) {
     std::normal_distribution<float> d((float)filler->num("mean", 0),
                                       (float)filler->num("std", 1));
     for (long i = 0; i < n; ++i) p[i] = d(rng);
+    if (sparse >= 0) {
+      // Bernoulli mask with p = sparse / shape(0), drawn after the values
+      // from the same engine: `sparse` is the mean number of non-zero
+      // weights over axis 0
+      CHECK_GE_(b.num_axes(), 1);
+      CHECK_LE_(sparse, (long)b.shape(0))
+          << "filler sparse: more non-zeros than shape(0) = " << b.shape(0);
+      std::bernoulli_distribution keep((double)sparse / b.shape(0));
+      for (long i = 0; i < n; ++i) p[i] *= keep(rng) ? 1.f : 0.f;
+    }
   } else if (type == "xavier" || type == "msra") {
     // filler.hpp:278-300 (xavier) / MSRAFiller: n = fan_in default,
     // AVERAGE/FAN_OUT via variance_norm
@@ -171,7 +188,7 @@ int g_syn_shape[3] = {0, 0, 0};
 void DataLayer::Reshape(const std::vector<Blob*>&,
                         const std::vector<Blob*>& top) {
   top[0]->Reshape({batch_, C_, H_, W_});
-  top[1]->Reshape({batch_});
+  if (top.size() > 1) top[1]->Reshape({batch_});
 }
 
 void DataLayer::Forward_cpu(const std::vector<Blob*>&,
@@ -188,10 +205,12 @@ void DataLayer::Forward_cpu(const std::vector<Blob*>&,
   const long n = top[0]->count();
   for (long i = 0; i < n; ++i)
     d[i] = h_u01(h_splitmix64(key ^ (uint64_t)i)) * 2.f - 1.f;
-  float* l = top[1]->mutable_cpu_data();
-  for (long i = 0; i < batch_; ++i)
-    l[i] = (float)(h_splitmix64(key ^ 0xABCDull ^ (uint64_t)i) %
-                   (uint64_t)E.syn_classes);
+  if (top.size() > 1) {
+    float* l = top[1]->mutable_cpu_data();
+    for (long i = 0; i < batch_; ++i)
+      l[i] = (float)(h_splitmix64(key ^ 0xABCDull ^ (uint64_t)i) %
+                     (uint64_t)E.syn_classes);
+  }
   ++iter_;
 }
 
@@ -1133,6 +1152,136 @@ void AccuracyLayer::Forward_cpu(const std::vector<Blob*>& bottom,
   top[0]->mutable_cpu_data()[0] = total ? (float)correct / total : 0.f;
 }
 
+// ---------------------------------------------------------------- Sigmoid
+void SigmoidLayer::Forward_cpu(const std::vector<Blob*>& bottom,
+                               const std::vector<Blob*>& top) {
+  const float* x = bottom[0]->cpu_data();
+  float* y = top[0]->mutable_cpu_data();
+  const long n = bottom[0]->count();
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < n; ++i) y[i] = sigmoid_value(x[i]);
+}
+
+void SigmoidLayer::Backward_cpu(const std::vector<Blob*>& top,
+                                const std::vector<bool>& prop_down,
+                                const std::vector<Blob*>& bottom) {
+  if (!prop_down[0]) return;
+  const float* y = top[0]->cpu_data();
+  const float* dy = top[0]->cpu_diff();
+  float* dx = bottom[0]->mutable_cpu_diff();
+  const long n = bottom[0]->count();
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < n; ++i) dx[i] = dy[i] * y[i] * (1.f - y[i]);
+}
+
+// ------------------------------------------------ SigmoidCrossEntropyLoss
+void SigmoidCrossEntropyLossLayer::LayerSetUp(const std::vector<Blob*>&,
+                                              const std::vector<Blob*>&) {
+  // the target bottom never gets a gradient (the reference fails in
+  // Backward; an explicit request is refused here, before any iteration)
+  auto pd = param_->strs("propagate_down");
+  if (pd.size() > 1 && pd[1] == "true")
+    CAMD_FATAL << type() << " layer '" << name()
+               << "' cannot backpropagate to label inputs "
+                  "(propagate_down: true for bottom 1)";
+}
+
+void SigmoidCrossEntropyLossLayer::Reshape(const std::vector<Blob*>& bottom,
+                                           const std::vector<Blob*>& top) {
+  CHECK_EQ_(bottom[0]->count(), bottom[1]->count())
+      << "SigmoidCrossEntropyLoss layer '" << name()
+      << "': inputs must have the same count";
+  top[0]->Reshape({1});
+}
+
+void SigmoidCrossEntropyLossLayer::Forward_cpu(
+    const std::vector<Blob*>& bottom, const std::vector<Blob*>& top) {
+  const float* x = bottom[0]->cpu_data();
+  const float* t = bottom[1]->cpu_data();
+  const long n = bottom[0]->count();
+  double loss = 0;
+  for (long i = 0; i < n; ++i) loss += (double)sigmoid_ce_term(x[i], t[i]);
+  top[0]->mutable_cpu_data()[0] = (float)(loss / bottom[0]->num());
+}
+
+void SigmoidCrossEntropyLossLayer::Backward_cpu(
+    const std::vector<Blob*>&, const std::vector<bool>& prop_down,
+    const std::vector<Blob*>& bottom) {
+  if (!prop_down[0]) return;
+  const float scale = loss(0) / (float)bottom[0]->num();
+  const float* x = bottom[0]->cpu_data();
+  const float* t = bottom[1]->cpu_data();
+  float* dx = bottom[0]->mutable_cpu_diff();
+  const long n = bottom[0]->count();
+  for (long i = 0; i < n; ++i) dx[i] = (sigmoid_value(x[i]) - t[i]) * scale;
+}
+
+// ---------------------------------------------------------- EuclideanLoss
+void EuclideanLossLayer::Reshape(const std::vector<Blob*>& bottom,
+                                 const std::vector<Blob*>& top) {
+  CHECK_EQ_(bottom[0]->count(), bottom[1]->count())
+      << "EuclideanLoss layer '" << name()
+      << "': inputs must have the same count";
+  CHECK_EQ_(bottom[0]->count(1), bottom[1]->count(1))
+      << "EuclideanLoss layer '" << name()
+      << "': inputs must have the same dimension";
+  top[0]->Reshape({1});
+}
+
+void EuclideanLossLayer::Forward_cpu(const std::vector<Blob*>& bottom,
+                                     const std::vector<Blob*>& top) {
+  const float* a = bottom[0]->cpu_data();
+  const float* b = bottom[1]->cpu_data();
+  const long n = bottom[0]->count();
+  double dot = 0;
+  for (long i = 0; i < n; ++i) {
+    const float d = a[i] - b[i];
+    dot += (double)(d * d);
+  }
+  top[0]->mutable_cpu_data()[0] = (float)(dot * (0.5 / bottom[0]->num()));
+}
+
+void EuclideanLossLayer::Backward_cpu(const std::vector<Blob*>&,
+                                      const std::vector<bool>& prop_down,
+                                      const std::vector<Blob*>& bottom) {
+  const float* a = bottom[0]->cpu_data();
+  const float* b = bottom[1]->cpu_data();
+  const long n = bottom[0]->count();
+  for (int k = 0; k < 2; ++k) {
+    if (!prop_down[k]) continue;
+    // sign as in euclidean_loss_layer.cpp:34-45; a zero loss weight still
+    // writes (zeros)
+    const float alpha = (k == 0 ? 1.f : -1.f) * loss(0) / bottom[k]->num();
+    float* d = bottom[k]->mutable_cpu_diff();
+    for (long i = 0; i < n; ++i) d[i] = alpha * (a[i] - b[i]);
+  }
+}
+
+// ---------------------------------------------------------------- Flatten
+void FlattenLayer::Reshape(const std::vector<Blob*>& bottom,
+                           const std::vector<Blob*>& top) {
+  CHECK_(top[0] != bottom[0])
+      << "Flatten layer '" << name() << "' does not run in-place";
+  auto fp = param_->sub("flatten_param");
+  const int axes = bottom[0]->num_axes();
+  int axis = fp ? (int)fp->inum("axis", 1) : 1;
+  int end_axis = fp ? (int)fp->inum("end_axis", -1) : -1;
+  if (axis < 0) axis += axes;
+  if (end_axis < 0) end_axis += axes;
+  CHECK_(axis >= 0 && axis < axes && end_axis >= axis && end_axis < axes)
+      << "Flatten layer '" << name() << "': axis " << axis << " .. end_axis "
+      << end_axis << " of a " << axes << "-axis bottom";
+  std::vector<int> shape;
+  for (int i = 0; i < axis; ++i) shape.push_back(bottom[0]->shape(i));
+  shape.push_back((int)bottom[0]->count(axis, end_axis + 1));
+  for (int i = end_axis + 1; i < axes; ++i)
+    shape.push_back(bottom[0]->shape(i));
+  top[0]->Reshape(shape);
+  CHECK_EQ_(top[0]->count(), bottom[0]->count());
+  top[0]->ShareData(*bottom[0]);
+  top[0]->ShareDiff(*bottom[0]);
+}
+
 // ----------------------------------------------------------------- Input
 // reference InputLayer: tops shaped by input_param, filled externally
 class InputLayer : public Layer {
@@ -1170,6 +1319,10 @@ REGISTER_LAYER("DummyData", DataLayer)
 REGISTER_LAYER("Convolution", ConvolutionLayer)
 REGISTER_LAYER("InnerProduct", InnerProductLayer)
 REGISTER_LAYER("Pooling", PoolingLayer)
+REGISTER_LAYER("Sigmoid", SigmoidLayer)
+REGISTER_LAYER("SigmoidCrossEntropyLoss", SigmoidCrossEntropyLossLayer)
+REGISTER_LAYER("EuclideanLoss", EuclideanLossLayer)
+REGISTER_LAYER("Flatten", FlattenLayer)
 // ---------------------------------------------------------------- Scale
 // Reference layers/scale_layer.cpp (+ bias inside, :121-134): channel-wise
 // y = x * scale[c] (+ bias[c]); the BVLC BatchNorm+Scale prototxt pattern.

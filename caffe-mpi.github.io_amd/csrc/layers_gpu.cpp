@@ -26,8 +26,9 @@ void DataLayer::Forward_gpu(const std::vector<Blob*>&,
       h_splitmix64(E.seed ^ ((uint64_t)E.rank << 40) ^ (E.data_iter << 8));
   gpu::fill_uniform(E.stream, top[0]->count(), key, 0, -1.f, 1.f,
                     top[0]->mutable_gpu_data());
-  gpu::fill_labels(E.stream, top[1]->count(), key, 0, E.syn_classes,
-                   top[1]->mutable_gpu_data());
+  if (top.size() > 1)
+    gpu::fill_labels(E.stream, top[1]->count(), key, 0, E.syn_classes,
+                     top[1]->mutable_gpu_data());
   ++iter_;
 }
 
@@ -622,6 +623,66 @@ void SoftmaxWithLossLayer::Backward_gpu(const std::vector<Blob*>& top,
                        bottom[1]->gpu_data(), outer_, C_, inner_, scale,
                        bottom[0]->mutable_gpu_diff());
   (void)top;
+}
+
+// ---------------------------------------------------------------- Sigmoid
+void SigmoidLayer::Forward_gpu(const std::vector<Blob*>& bottom,
+                               const std::vector<Blob*>& top) {
+  gpu::sigmoid_fwd(Engine::get().stream, bottom[0]->gpu_data(),
+                   bottom[0]->count(), top[0]->mutable_gpu_data());
+}
+
+void SigmoidLayer::Backward_gpu(const std::vector<Blob*>& top,
+                                const std::vector<bool>& prop_down,
+                                const std::vector<Blob*>& bottom) {
+  if (!prop_down[0]) return;
+  gpu::sigmoid_bwd(Engine::get().stream, top[0]->gpu_data(),
+                   top[0]->gpu_diff(), bottom[0]->count(),
+                   bottom[0]->mutable_gpu_diff());
+}
+
+// ------------------------------------- SigmoidCrossEntropyLoss, Euclidean
+static double* loss_partials_ws(long n) {
+  return (double*)Workspace::get_global().get(
+      Workspace::kLossPart, sizeof(double) * gpu::loss_partials(n));
+}
+
+void SigmoidCrossEntropyLossLayer::Forward_gpu(
+    const std::vector<Blob*>& bottom, const std::vector<Blob*>& top) {
+  const long n = bottom[0]->count();
+  gpu::sigmoid_ce_fwd(Engine::get().stream, bottom[0]->gpu_data(),
+                      bottom[1]->gpu_data(), n, bottom[0]->num(),
+                      loss_partials_ws(n), top[0]->mutable_gpu_data());
+}
+
+void SigmoidCrossEntropyLossLayer::Backward_gpu(
+    const std::vector<Blob*>&, const std::vector<bool>& prop_down,
+    const std::vector<Blob*>& bottom) {
+  if (!prop_down[0]) return;
+  gpu::sigmoid_ce_bwd(Engine::get().stream, bottom[0]->gpu_data(),
+                      bottom[1]->gpu_data(), bottom[0]->count(),
+                      loss(0) / (float)bottom[0]->num(),
+                      bottom[0]->mutable_gpu_diff());
+}
+
+void EuclideanLossLayer::Forward_gpu(const std::vector<Blob*>& bottom,
+                                     const std::vector<Blob*>& top) {
+  const long n = bottom[0]->count();
+  gpu::euclid_fwd(Engine::get().stream, bottom[0]->gpu_data(),
+                  bottom[1]->gpu_data(), n, bottom[0]->num(),
+                  loss_partials_ws(n), top[0]->mutable_gpu_data());
+}
+
+void EuclideanLossLayer::Backward_gpu(const std::vector<Blob*>&,
+                                      const std::vector<bool>& prop_down,
+                                      const std::vector<Blob*>& bottom) {
+  if (!prop_down[0] && !prop_down[1]) return;
+  gpu::euclid_bwd(
+      Engine::get().stream, bottom[0]->gpu_data(), bottom[1]->gpu_data(),
+      bottom[0]->count(), loss(0) / bottom[0]->num(),
+      prop_down[0] ? bottom[0]->mutable_gpu_diff() : nullptr,
+      -loss(0) / bottom[1]->num(),
+      prop_down[1] ? bottom[1]->mutable_gpu_diff() : nullptr);
 }
 
 }  // namespace camd

@@ -94,6 +94,26 @@ CAMD_HD inline float solver_rule_step(float g, float w, float& h, float& h2,
   }
 }
 
+// ------------------------------------------------- sigmoid and its losses
+// Per-element formulas of the reference's sigmoid_layer.cpp:10 and
+// sigmoid_cross_entropy_loss_layer.cpp:41-44.  As with the solver rules, one
+// function serves the CPU loops and the GPU kernels.  expf / logf are the
+// IEEE library forms: a NaN input stays NaN, exp overflow gives inf, so the
+// sigmoid saturates to exactly 0 or 1 and never produces NaN for finite x.
+// log(1 + exp(.)) is written as the reference writes it, not as log1pf: on
+// gfx950 log1pf made the loss forward 2.5x slower than HBM allows
+// (profiles/sigmoid_loss_kernels.txt), and the argument of the log is in
+// [1, 2], where the plain form is off by at most one float rounding of it.
+CAMD_HD inline float sigmoid_value(float x) {
+  return 1.f / (1.f + expf(-x));
+}
+// the term the cross-entropy loss SUMS (already negated):
+// -(x*(t - [x>=0]) - log(1 + exp(x - 2x*[x>=0])))
+CAMD_HD inline float sigmoid_ce_term(float x, float t) {
+  const float pos = x >= 0.f ? 1.f : 0.f;
+  return logf(1.f + expf(x - 2.f * x * pos)) - x * (t - pos);
+}
+
 // --------------------------------------------------------- exact fast division
 // n / d for 0 <= n < 2^31 and 1 <= d <= 2^31 as multiply-high, add and shift
 // (Granlund & Montgomery's round-up form: with l = ceil(log2 d) and
@@ -204,6 +224,10 @@ void gemm_trace_readers(long* cursor, long* wide64);
 //   op=sgd_seg lo=<lo> hi=<hi> nseg=<nseg>
 //   op=solver_seg rule=<sgd|nesterov|adagrad|rmsprop|adadelta|adam>
 //       reg=<L1|L2> lo=<lo> hi=<hi> nseg=<nseg>
+//   op=sigmoid_fwd|sigmoid_bwd|sigmoid_ce_bwd|euclid_bwd n=<elements>
+//       blocks=<grid> passes=<grid-stride passes of the busiest thread>
+//   op=sigmoid_ce_fwd|euclid_fwd n=<elements> blocks=<grid>
+//       partials=<doubles the final sum adds> passes=<as above>
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
 
@@ -291,6 +315,30 @@ void softmaxloss_fwd(hipStream_t s, const float* prob, const float* label,
                      int outer, int C, int inner, float* loss_out);
 void softmaxloss_bwd(hipStream_t s, const float* prob, const float* label,
                      int outer, int C, int inner, float scale, float* dx);
+
+// Sigmoid (sigmoid_layer.cu): y = 1 / (1 + exp(-x)), x == y allowed;
+// dx = dy * y * (1 - y) from the TOP data, so in-place needs no saved input.
+// Stores past n are masked (the float4 pack at the edge is loaded whole).
+void sigmoid_fwd(hipStream_t s, const float* x, long n, float* y);
+void sigmoid_bwd(hipStream_t s, const float* y, const float* dy, long n,
+                 float* dx);
+
+// Loss sums over n elements, deterministic and two-stage: a fixed grid
+// writes one double per block into `partials` (loss_partials(n) doubles),
+// then one block adds them in a fixed order and writes loss_out[0].
+int loss_partials(long n);
+// SigmoidCrossEntropyLoss: Σ sigmoid_ce_term(x, t) / num; σ(x) is never
+// materialised, the backward recomputes it: dx = (σ(x) - t) * scale
+void sigmoid_ce_fwd(hipStream_t s, const float* x, const float* t, long n,
+                    int num, double* partials, float* loss_out);
+void sigmoid_ce_bwd(hipStream_t s, const float* x, const float* t, long n,
+                    float scale, float* dx);
+// EuclideanLoss: Σ (a - b)² / num / 2; backward recomputes a - b and writes
+// da = scale_a * (a - b) and/or db = scale_b * (a - b) (null = not wanted)
+void euclid_fwd(hipStream_t s, const float* a, const float* b, long n,
+                int num, double* partials, float* loss_out);
+void euclid_bwd(hipStream_t s, const float* a, const float* b, long n,
+                float scale_a, float* da, float scale_b, float* db);
 
 // out[n] = Σ_m A[m][n] — IP bias grad (deterministic)
 void colsum(hipStream_t s, const float* A, long M, long N, float* out);

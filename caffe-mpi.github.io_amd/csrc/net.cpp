@@ -5,25 +5,48 @@
 
 namespace camd {
 
-namespace {
-// does this layer message run in `phase`? (include/exclude NetStateRule
-// subset — only `phase` is used by the four model sets)
-bool layer_in_phase(const PMsgPtr& lm, Phase phase) {
-  const char* want = phase == Phase::TRAIN ? "TRAIN" : "TEST";
-  auto incs = lm->subs("include");
-  if (!incs.empty()) {
-    for (auto& r : incs)
-      if (r->str("phase") == want) return true;
+bool state_meets_rule(const NetState& state, const PMsg& rule) {
+  auto has_stage = [&](const std::string& st) {
+    for (auto& s : state.stages)
+      if (s == st) return true;
     return false;
-  }
-  for (auto& r : lm->subs("exclude"))
-    if (r->str("phase") == want) return false;
+  };
+  if (rule.has("phase") &&
+      rule.str("phase") != (state.phase == Phase::TRAIN ? "TRAIN" : "TEST"))
+    return false;
+  if (rule.has("min_level") && state.level < rule.inum("min_level"))
+    return false;
+  if (rule.has("max_level") && state.level > rule.inum("max_level"))
+    return false;
+  for (auto& st : rule.strs("stage"))
+    if (!has_stage(st)) return false;
+  for (auto& st : rule.strs("not_stage"))
+    if (has_stage(st)) return false;
   return true;
 }
-}  // namespace
+
+bool layer_in_state(const PMsg& lm, const NetState& state) {
+  auto incs = lm.subs("include");
+  auto excs = lm.subs("exclude");
+  CHECK_(incs.empty() || excs.empty())
+      << "layer '" << lm.str("name")
+      << "': specify either include rules or exclude rules; not both";
+  bool included = incs.empty();
+  for (auto& r : excs)
+    if (included && state_meets_rule(state, *r)) included = false;
+  for (auto& r : incs)
+    if (!included && state_meets_rule(state, *r)) included = true;
+  return included;
+}
 
 Net::Net(const PMsgPtr& net_param, Phase phase, int batch_override)
     : phase_(phase) {
+  state_.phase = phase;
+  init(net_param, batch_override);
+}
+
+Net::Net(const PMsgPtr& net_param, const NetState& state, int batch_override)
+    : phase_(state.phase), state_(state) {
   init(net_param, batch_override);
 }
 
@@ -96,7 +119,7 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
   name_ = msg->str("name");
   std::vector<PMsgPtr> lmsgs;
   for (auto& lm : msg->subs("layer"))
-    if (layer_in_phase(lm, phase_)) {
+    if (layer_in_state(*lm, state_)) {
       // shallow-clone: insert_splits rewrites bottom names in place, and
       // the source tree is shared with other nets (train/test pair)
       auto copy = std::make_shared<PMsg>(*lm);
@@ -119,7 +142,14 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
     for (auto& t : lm->strs("top")) {
       auto it = blob_map_.find(t);
       if (it != blob_map_.end()) {
-        // in-place: top name equals an existing blob (must be a bottom)
+        // in-place: top name equals an existing blob (must be a bottom).
+        // A layer WITHOUT bottoms cannot be in-place: its top would
+        // overwrite another layer's (reference net.cpp AppendTop) — two
+        // staged Data layers that the net state did not tell apart
+        CHECK_(!lm->strs("bottom").empty())
+            << "layer '" << layer->name() << "': top blob '" << t
+            << "' is produced by more than one layer (do its include "
+               "rules need a stage or level of the net state?)";
         top.push_back(it->second.get());
       } else {
         auto nb = std::make_shared<Blob>();
@@ -150,6 +180,7 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
     layers_.push_back(layer);
     bottoms_.push_back(bottom);
     tops_.push_back(top);
+    top_names_.push_back(lm->strs("top"));
   }
 
   // need-backward / propagate-down flags (net.cpp Init bottom-up logic;
@@ -167,18 +198,31 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
       prop_down_[i][b] = blob_needs[bottoms_[i][b]];
       need = need || prop_down_[i][b];
     }
+    // LayerParameter.propagate_down (reference net.cpp Init): one entry per
+    // bottom, false cuts that bottom's gradient
+    const auto pd = layers_[i]->param()->strs("propagate_down");
+    if (!pd.empty()) {
+      CHECK_EQ_(pd.size(), bottoms_[i].size())
+          << "layer '" << layers_[i]->name()
+          << "': propagate_down must be given for every bottom or for none";
+      need = !layers_[i]->blobs().empty();
+      for (size_t b = 0; b < bottoms_[i].size(); ++b) {
+        if (pd[b] != "true" && pd[b] != "1") prop_down_[i][b] = false;
+        need = need || prop_down_[i][b];
+      }
+    }
     if (is_source) need = false;
     if (force && !is_source) {
       need = true;
       for (size_t b = 0; b < bottoms_[i].size(); ++b)
-        prop_down_[i][b] = blob_needs.count(bottoms_[i][b])
-                               ? blob_needs[bottoms_[i][b]]
-                               : false;
+        prop_down_[i][b] =
+            blob_needs.count(bottoms_[i][b]) && blob_needs[bottoms_[i][b]] &&
+            (pd.empty() || pd[b] == "true" || pd[b] == "1");
     }
     layer_need_bwd_[i] = need;
     for (auto* t : tops_[i])
-      blob_needs[t] = need || (force && !is_source &&
-                               layers_[i]->type() != "SoftmaxWithLoss");
+      blob_needs[t] =
+          need || (force && !is_source && !layers_[i]->is_loss_layer());
   }
 
   // learnable params in backward-completion order (reverse layer order)
@@ -370,16 +414,48 @@ float Net::loss() {
   return total;
 }
 
-std::vector<std::pair<std::string, float>> Net::scores() {
+std::vector<Net::Score> Net::scores() {
   Engine::get().sync();
-  std::vector<std::pair<std::string, float>> out;
+  std::vector<Score> out;
   for (size_t i = 0; i < layers_.size(); ++i)
     for (size_t t = 0; t < tops_[i].size(); ++t) {
       const bool acc = layers_[i]->type() == "Accuracy";
-      if (layers_[i]->loss((int)t) != 0.f || acc)
-        out.emplace_back(layers_[i]->name(), tops_[i][t]->cpu_data()[0]);
+      if (layers_[i]->loss((int)t) != 0.f || acc ||
+          layers_[i]->is_loss_layer())
+        out.push_back({layers_[i]->name(), top_names_[i][t],
+                       (double)tops_[i][t]->cpu_data()[0], std::string()});
     }
+  for (auto& s : out) {
+    int same = 0;
+    for (auto& o : out) same += o.layer == s.layer;
+    s.label = same > 1 ? s.top : s.layer;
+  }
   return out;
+}
+
+std::vector<Net::Score> Net::test_scores(long iters) {
+  // the data feeds key on Engine::data_iter: advance it per forward so
+  // successive test iterations see successive batches (with LMDB this
+  // walks the set in order from record 0 — a fixed eval set)
+  Engine& E = Engine::get();
+  const uint64_t saved_iter = E.data_iter;
+  std::vector<Score> sum;
+  for (long it = 0; it < iters; ++it) {
+    E.data_iter = (uint64_t)it;
+    Forward();
+    auto sc = scores();
+    if (it == 0) {
+      sum = sc;
+    } else {
+      for (size_t k = 0; k < sum.size(); ++k) sum[k].value += sc[k].value;
+    }
+  }
+  E.data_iter = saved_iter;
+  for (auto& s : sum) s.value /= (double)iters;
+  std::stable_sort(sum.begin(), sum.end(), [](const Score& a, const Score& b) {
+    return a.label < b.label;
+  });
+  return sum;
 }
 
 std::vector<std::string> Net::blob_names() const {

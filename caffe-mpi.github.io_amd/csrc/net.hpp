@@ -23,15 +23,46 @@ struct ReduceHook {
   virtual ~ReduceHook() = default;
 };
 
+// reference NetState (caffe.proto): what a layer's include / exclude rules
+// are matched against
+struct NetState {
+  Phase phase = Phase::TRAIN;
+  int level = 0;
+  std::vector<std::string> stages;
+};
+// reference Net::StateMeetsRule (net.cpp:435-499): phase equal, level within
+// [min_level, max_level], every `stage` present, no `not_stage` present
+bool state_meets_rule(const NetState& state, const PMsg& rule);
+// reference Net::FilterNet (net.cpp:407-433): included by default unless an
+// exclude rule is met; with include rules, only when one of them is met
+bool layer_in_state(const PMsg& layer_msg, const NetState& state);
+
 class Net {
  public:
+  // level 0, no stages
   Net(const PMsgPtr& net_param, Phase phase, int batch_override = 0);
+  Net(const PMsgPtr& net_param, const NetState& state,
+      int batch_override = 0);
 
   void Forward();
   void Backward(ReduceHook* hook = nullptr);
   float loss();  // syncs; Σ loss_weight · loss-top
-  // test-score outputs: every loss-weighted top + every Accuracy top
-  std::vector<std::pair<std::string, float>> scores();
+  // test-score outputs: every top of a loss layer (also at loss_weight 0,
+  // which the reference reports too), every other loss-weighted top and
+  // every Accuracy top, one entry per (layer, top) in net order
+  struct Score {
+    std::string layer, top;  // names of the layer and of the top blob
+    double value;
+    // what the score is printed under: the layer name, or the top blob's
+    // name (as the reference prints) where two scored tops share a layer
+    // name
+    std::string label;
+  };
+  std::vector<Score> scores();
+  // reference Solver::Test (solver.cpp:439-540) for one net: `iters`
+  // forwards over successive batches from data position 0, every score
+  // averaged; sorted by label.  Leaves Engine::data_iter as it found it.
+  std::vector<Score> test_scores(long iters);
 
   struct LParam {
     Blob* blob;
@@ -71,6 +102,7 @@ class Net {
   std::vector<std::string> blob_names() const;
   const std::string& name() const { return name_; }
   Phase phase() const { return phase_; }
+  const NetState& state() const { return state_; }
 
   // copy weights from another net (test-net sharing / snapshot restore)
   void ShareTrainedLayersWith(Net& other);
@@ -92,6 +124,8 @@ class Net {
   Phase phase_;
   std::vector<std::shared_ptr<Layer>> layers_;
   std::vector<std::vector<Blob*>> bottoms_, tops_;
+  std::vector<std::vector<std::string>> top_names_;
+  NetState state_;
   std::vector<std::vector<bool>> prop_down_;
   std::vector<bool> layer_need_bwd_;
   std::map<std::string, std::shared_ptr<Blob>> blob_map_;

@@ -131,7 +131,8 @@ Solver::Solver(const PMsgPtr& sp, int batch_override) : param_(sp) {
     E.seed = (uint64_t)sp->inum("random_seed");
     E.cpu_rng.seed(E.seed + (uint64_t)E.rank);  // +rank: parallel.cpp:179-187
   }
-  net_.reset(new Net(net_msg, Phase::TRAIN, batch_override));
+  parse_states();
+  net_.reset(new Net(net_msg, train_state_, batch_override));
   weight_decay_ = (float)sp->num("weight_decay", 0.0);
   const long nparams = (long)net_->learnable_params().size();
   const long buckets = sp->inum("reduce_buckets", 6);  // caffe.proto:140
@@ -385,7 +386,6 @@ void Solver::Step(int iters) {
   using clock = std::chrono::steady_clock;
   const long display = param_->inum("display", 0);
   const long test_interval = param_->inum("test_interval", 0);
-  const long test_iter = param_->inum("test_iter", 1);
   const long snap_interval = param_->inum("snapshot", 0);
   // gradient accumulation: iter_size fwd/bwd passes per update, diffs
   // accumulate in the arena, one reduce+update scaled by 1/iter_size
@@ -417,7 +417,7 @@ void Solver::Step(int iters) {
     }
     if (test_interval > 0 && iter_ > 0 && iter_ % test_interval == 0 &&
         test_net())
-      TestAll(test_iter);
+      TestAll();
     cur_lr_ = GetLearningRate();
     cur_mom_ = GetMomentum();
     upd_lr_ = cur_lr_;
@@ -525,52 +525,89 @@ void Solver::print_perf_report() const {
           Engine::get().device, ratio, batch, ratio * batch);
 }
 
-Net* Solver::test_net() {
-  if (test_net_) return test_net_.get();
-  // only build when the net defines TEST-phase layers
-  bool has_test = false;
-  for (auto& lm : net_msg_->subs("layer")) {
-    for (auto& inc : lm->subs("include"))
-      if (inc->str("phase") == "TEST") has_test = true;
+// train_state and every test_state of the solver file (reference
+// Solver::InitTrainNet / InitTestNets: the phase is fixed, level and stages
+// come from the state message), and the test_iter of every test net
+void Solver::parse_states() {
+  auto read = [](const PMsgPtr& m, Phase phase) {
+    NetState st;
+    st.phase = phase;
+    if (m) {
+      st.level = (int)m->inum("level", 0);
+      st.stages = m->strs("stage");
+    }
+    return st;
+  };
+  train_state_ = read(param_->sub("train_state"), Phase::TRAIN);
+  for (auto& m : param_->subs("test_state"))
+    test_states_.push_back(read(m, Phase::TEST));
+  test_iters_ = param_->inums("test_iter");
+  if (!test_states_.empty()) {
+    if (test_iters_.size() != test_states_.size())
+      CAMD_FATAL << "solver gives " << test_states_.size()
+                 << " test_state entries but " << test_iters_.size()
+                 << " test_iter entries: test_iter must be given once per "
+                    "test net";
+  } else {
+    // no test_state: at most one default TEST net, one test_iter (default 1)
+    if (test_iters_.size() > 1)
+      CAMD_FATAL << "solver gives " << test_iters_.size()
+                 << " test_iter entries but 1 test net (no test_state): "
+                    "test_iter must be given once per test net";
+    if (test_iters_.empty()) test_iters_.push_back(1);
   }
-  if (!has_test) return nullptr;
-  test_net_.reset(new Net(net_msg_, Phase::TEST));
-  test_net_->ShareTrainedLayersWith(*net_);
-  return test_net_.get();
 }
 
-void Solver::TestAll(long iters) {
+int Solver::num_test_nets() {
+  if (!test_nets_built_) {
+    test_nets_built_ = true;
+    std::vector<NetState> states = test_states_;
+    if (states.empty()) {
+      // only build when the net defines TEST-phase layers
+      bool has_test = false;
+      for (auto& lm : net_msg_->subs("layer")) {
+        for (auto& inc : lm->subs("include"))
+          if (inc->str("phase") == "TEST") has_test = true;
+      }
+      if (has_test) {
+        NetState st;
+        st.phase = Phase::TEST;
+        states.push_back(st);
+      }
+    }
+    for (auto& st : states) {
+      test_nets_.emplace_back(new Net(net_msg_, st));
+      test_nets_.back()->ShareTrainedLayersWith(*net_);
+    }
+  }
+  return (int)test_nets_.size();
+}
+
+Net* Solver::test_net(int i) {
+  return i >= 0 && i < num_test_nets() ? test_nets_[i].get() : nullptr;
+}
+
+void Solver::TestAll(long iters_override) {
   // reference: the test pass runs on the root solver only (solver.cpp:439;
   // cross-rank SharedScores aggregation is multi-node machinery)
   if (Engine::get().rank != 0) return;
-  Net* tn = test_net();
-  if (!tn) return;
-  // average every loss-weighted / Accuracy top over the test iterations
-  // (reference Solver::Test, solver.cpp:439-540; cross-rank SharedScores
-  // aggregation is multi-node machinery — single-node here)
-  std::map<std::string, double> scores;
-  // the data feeds key on Engine::data_iter: advance it per TEST forward
-  // so successive test iterations see successive batches (with LMDB this
-  // walks the test set in order from record 0 — a fixed eval set; the
-  // training stream is unaffected, Step re-pins data_iter each train
-  // iteration).  Without this every test iteration repeated ONE batch.
-  Engine& E = Engine::get();
-  const uint64_t saved_iter = E.data_iter;
-  for (long it = 0; it < iters; ++it) {
-    E.data_iter = (uint64_t)it;
-    tn->Forward();
-    for (auto& kv : tn->scores()) scores[kv.first] += kv.second;
-  }
-  E.data_iter = saved_iter;
-  for (auto& kv : scores) {
-    const double v = kv.second / iters;
-    fprintf(stderr, "[caffe_amd] Test net output: %s = %g\n",
-            kv.first.c_str(), v);
-    if (!std::isfinite(v))
-      fprintf(stderr,
-              "[caffe_amd] WARNING: non-finite test score for %s — the net "
-              "is diverging (or untrained BN stats at iter 0)\n",
-              kv.first.c_str());
+  const int n = num_test_nets();
+  for (int i = 0; i < n; ++i) {
+    if (n > 1)
+      fprintf(stderr, "[caffe_amd] Iteration %ld, Testing net (#%d)\n", iter_,
+              i);
+    const long iters = iters_override > 0 ? iters_override : test_iters_[i];
+    // average every scored top over the test iterations (reference
+    // Solver::Test, solver.cpp:439-540)
+    for (auto& sc : test_nets_[i]->test_scores(iters)) {
+      fprintf(stderr, "[caffe_amd] Test net output: %s = %g\n",
+              sc.label.c_str(), sc.value);
+      if (!std::isfinite(sc.value))
+        fprintf(stderr,
+                "[caffe_amd] WARNING: non-finite test score for %s — the net "
+                "is diverging (or untrained BN stats at iter 0)\n",
+                sc.label.c_str());
+    }
   }
 }
 

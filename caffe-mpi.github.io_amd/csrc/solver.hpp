@@ -73,8 +73,14 @@ class Solver {
   float GetMomentum() const { return (float)param_->num("momentum", 0.0); }
 
   Net& net() { return *net_; }
-  Net* test_net();  // lazily built TEST-phase net sharing train weights
-  void TestAll(long iters);  // solver.cpp:439-540 semantics
+  // TEST nets sharing the train weights, built lazily: one per test_state
+  // of the solver file, or one default TEST net when it has none and the
+  // net defines TEST-phase layers (reference Solver::InitTestNets)
+  int num_test_nets();
+  Net* test_net(int i = 0);  // null when there is none
+  // every test net for its own test_iter (solver.cpp:439-540 semantics), or
+  // for `iters_override` iterations each when that is > 0
+  void TestAll(long iters_override = 0);
   void Snapshot();           // .caffemodel + .solverstate (solver.cpp:542)
   // reference per-GPU perf report (solver.cpp:619-628): iters/sec x batch,
   // skipping the first two measured iterations like the reference (:299)
@@ -130,7 +136,12 @@ class Solver {
   PMsgPtr param_;
   PMsgPtr net_msg_;
   std::unique_ptr<Net> net_;
-  std::unique_ptr<Net> test_net_;
+  std::vector<std::unique_ptr<Net>> test_nets_;
+  bool test_nets_built_ = false;
+  std::vector<NetState> test_states_;  // parsed at construction
+  std::vector<long> test_iters_;       // one per test net
+  void parse_states();
+  NetState train_state_;
   std::unique_ptr<Comm> comm_;
   Reducer reducer_{this};
   ActionRequestFn action_fn_ = nullptr;

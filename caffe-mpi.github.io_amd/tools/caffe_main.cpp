@@ -1,7 +1,8 @@
 // caffe_main.cpp — the reference CLI surface (tools/caffe.cpp:28-46,:120):
 //   caffe train -solver=... [-gpu=0|all] [-snapshot=...] [-weights=...]
 //   caffe test  -model=... -weights=... [-gpu=0] [-iterations=50]
-//   caffe time  -model=... [-gpu=0] [-iterations=50]
+//               [-stage=a,b] [-level=0]
+//   caffe time  -model=... [-gpu=0] [-iterations=50] [-stage=a,b] [-level=0]
 //   caffe device_query [-gpu=0]
 // Single-process/single-GPU here ("all" selects device 0); multi-GPU
 // training runs one process per GPU through bench.py / the C ABI
@@ -90,6 +91,23 @@ static std::map<std::string, std::string> parse_flags(int argc, char** argv,
     }
   }
   return flags;
+}
+
+// -stage (comma list) and -level of `test` and `time` (tools/caffe.cpp
+// get_stages_from_flags, FLAGS_level): the NetState the net is filtered by
+static NetState state_from_flags(std::map<std::string, std::string>& flags,
+                                 Phase phase) {
+  NetState st;
+  st.phase = phase;
+  if (flags.count("level")) st.level = atoi(flags["level"].c_str());
+  const std::string list = flags.count("stage") ? flags["stage"] : "";
+  for (size_t pos = 0; pos < list.size();) {
+    size_t next = list.find(',', pos);
+    if (next == std::string::npos) next = list.size();
+    if (next > pos) st.stages.push_back(list.substr(pos, next - pos));
+    pos = next + 1;
+  }
+  return st;
 }
 
 static void setup_device(const std::map<std::string, std::string>& flags) {
@@ -403,28 +421,24 @@ int main(int argc, char** argv) {
     if (cmd == "test") {
       CHECK_(flags.count("model")) << "test needs -model";
       setup_device(flags);
-      Net net(parse_prototxt_file(flags["model"]), Phase::TEST);
+      Net net(parse_prototxt_file(flags["model"]),
+              state_from_flags(flags, Phase::TEST));
       if (flags.count("weights")) net.LoadWeights(flags["weights"]);
       const int iters = flags.count("iterations")
                             ? atoi(flags["iterations"].c_str())
                             : 50;
-      std::map<std::string, double> scores;
-      for (int i = 0; i < iters; ++i) {
-        // advance the data-stream cursor per iteration (successive test
-        // batches; with LMDB this walks the set from record 0)
-        Engine::get().data_iter = (uint64_t)i;
-        net.Forward();
-        for (auto& kv : net.scores()) scores[kv.first] += kv.second;
-      }
-      for (auto& kv : scores)
-        printf("%s = %g\n", kv.first.c_str(), kv.second / iters);
+      // successive test batches (with LMDB the set from record 0), every
+      // scored top averaged
+      for (auto& sc : net.test_scores(iters))
+        printf("%s = %g\n", sc.label.c_str(), sc.value);
       return 0;
     }
     if (cmd == "time") {
       CHECK_(flags.count("model")) << "time needs -model";
       setup_device(flags);
       Engine::get().seed = 1371;  // tools/caffe.cpp:365 pins 1371
-      Net net(parse_prototxt_file(flags["model"]), Phase::TRAIN);
+      Net net(parse_prototxt_file(flags["model"]),
+              state_from_flags(flags, Phase::TRAIN));
       const int iters = flags.count("iterations")
                             ? atoi(flags["iterations"].c_str())
                             : 10;

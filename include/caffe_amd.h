@@ -74,6 +74,18 @@ long caffe_solver_iter(caffe_solver_t s);
  * — syncs */
 float caffe_solver_loss(caffe_solver_t s);
 caffe_net_t caffe_solver_net(caffe_solver_t s);
+/* Solver::test_nets() (solver.hpp): one TEST net per test_state of the
+ * solver file, or one default TEST net when the net has TEST-phase layers
+ * (Solver::InitTestNets, solver.cpp); they share the trained weights and
+ * are owned by the solver.  -1 / NULL on error. */
+int caffe_solver_num_test_nets(caffe_solver_t s);
+caffe_net_t caffe_solver_test_net(caffe_solver_t s, int i);
+/* Solver::Test(test_net_id) (solver.cpp:439-540): `iters` forwards of test
+ * net i over successive batches, every scored top averaged.  Writes up to
+ * max_scores values and the newline-joined top-blob names of ALL scores
+ * (truncated to name_cap); returns the number of scores, -1 on error. */
+int caffe_solver_test(caffe_solver_t s, int i, int iters, char* names_out,
+                      int name_cap, float* values_out, int max_scores);
 
 /* Solver::Snapshot / Restore (solver.cpp:542-604; .caffemodel binaryproto
  * weights + .solverstate with SGD history, sgd_solver.cpp:262-353) */
@@ -118,6 +130,13 @@ int caffe_comm_set_callback(caffe_solver_t s, caffe_allreduce_cb cb,
 /* Net construction for inference/parity runs (Net::Init, net.cpp:64) */
 caffe_net_t caffe_net_create(const char* net_prototxt_path, int phase,
                              int batch_override);
+/* the same with a NetState (the reference's Net(param_file, phase, level,
+ * stages) constructor, net.hpp; NetState level / stage, caffe.proto):
+ * `stages` is a comma-separated list, NULL or "" for none.  Layers are kept
+ * by Net::FilterNet / StateMeetsRule (net.cpp:407-499) */
+caffe_net_t caffe_net_create_state(const char* net_prototxt_path, int phase,
+                                   int level, const char* stages,
+                                   int batch_override);
 void caffe_net_free(caffe_net_t n);
 int caffe_net_forward(caffe_net_t n);           /* net.cpp:692 */
 int caffe_net_backward(caffe_net_t n);          /* net.cpp:1031 */
