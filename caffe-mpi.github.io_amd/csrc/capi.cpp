@@ -596,6 +596,28 @@ int caffe_kernel_trace_read(char* buf, int cap) {
   API_CATCH
 }
 
+int caffe_net_fusions(caffe_net_t n, char* buf, int cap) {
+  API_TRY
+  static const char* const kinds[] = {"bn_relu", "conv_relu", "sum_relu",
+                                      "bn_add", "bn_add_relu"};
+  auto& layers = N(n)->layers();
+  std::string text;
+  if (cap > 0) buf[0] = 0;
+  for (auto& f : N(n)->fusions()) {
+    std::string line = std::string(kinds[f.kind]) + " " +
+                       layers[f.producer]->name();
+    for (size_t k = 0; k < f.absorbed.size(); ++k)
+      line += (k ? "," : " ") + layers[f.absorbed[k]]->name();
+    line += "\n";
+    // whole lines only, like the trace readers
+    if ((long)(text.size() + line.size()) < (long)cap)
+      memcpy(buf + text.size(), line.c_str(), line.size() + 1);
+    text += line;
+  }
+  return (int)text.size();
+  API_CATCH
+}
+
 int caffe_perf_reset(void) {
   for (auto& kv : Engine::get().perf()) {
     kv.second.launches = 0;

@@ -7,10 +7,20 @@ Engine& Engine::get() {
   return e;
 }
 
-const char*& error_context() {
-  thread_local const char* ctx = nullptr;
+namespace {
+std::string& error_text() {
+  thread_local std::string ctx;
   return ctx;
 }
+}  // namespace
+
+const std::string& error_context() { return error_text(); }
+
+ErrorScope::ErrorScope(std::string text) : prev_(std::move(error_text())) {
+  error_text() = std::move(text);
+}
+
+ErrorScope::~ErrorScope() { error_text() = std::move(prev_); }
 
 void Engine::set_mode_gpu(int dev) {
   mode = Mode::GPU;

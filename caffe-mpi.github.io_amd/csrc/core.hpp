@@ -33,11 +33,23 @@
 namespace camd {
 
 // ---------------------------------------------------------------- logging
-// error-context breadcrumb: Net sets this to "layer 'conv1' (Convolution)
-// Reshape" etc. before dispatching into layer code, so a CHECK failure
-// deep in Blob/kernel plumbing names the layer it fired under (round-1
-// review: a bare "CHECK failed: (d) >= (0)" was undiagnosable)
-const char*& error_context();
+// error-context breadcrumb: Net opens an ErrorScope reading "layer 'conv1'
+// (Convolution) Reshape" etc. around every dispatch into layer code, so a
+// CHECK failure deep in Blob/kernel plumbing names the layer it fired under
+// (round-1 review: a bare "CHECK failed: (d) >= (0)" was undiagnosable).
+// The text is per thread and owned here; a scope puts the previous text
+// back when it ends, also when a CHECK throws through it.
+const std::string& error_context();  // empty outside every scope
+class ErrorScope {
+ public:
+  explicit ErrorScope(std::string text);
+  ~ErrorScope();
+  ErrorScope(const ErrorScope&) = delete;
+  ErrorScope& operator=(const ErrorScope&) = delete;
+
+ private:
+  std::string prev_;
+};
 
 struct FatalStream {
   std::ostringstream ss;
@@ -46,7 +58,7 @@ struct FatalStream {
   FatalStream(const char* f, int l) : file(f), line(l) {}
   [[noreturn]] ~FatalStream() noexcept(false) {
     std::string msg = ss.str();
-    if (error_context()) {
+    if (!error_context().empty()) {
       msg += " [in ";
       msg += error_context();
       msg += "]";

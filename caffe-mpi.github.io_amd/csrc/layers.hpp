@@ -415,6 +415,13 @@ class EltwiseLayer : public Layer {
                     const std::vector<Blob*>&) override;
   std::vector<float> coeffs_;
   std::string op_ = "SUM";
+  // a plain sum: what the add3 forward, the diff-aliasing backward and
+  // the graph fusions require
+  bool unit_sum() const {
+    bool ones = op_ == "SUM";
+    for (float c : coeffs_) ones = ones && c == 1.f;
+    return ones;
+  }
   bool fuse_relu_ = false;  // GPU graph fusion: SUM+ReLU forward in one pass
   bool fused_away_ = false;  // producing BN writes bn(x)+other directly
 };

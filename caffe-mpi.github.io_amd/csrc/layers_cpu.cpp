@@ -752,11 +752,20 @@ void EltwiseLayer::LayerSetUp(const std::vector<Blob*>& bottom,
                               const std::vector<Blob*>&) {
   auto ep = param_->sub("eltwise_param");
   op_ = ep ? ep->str("operation", "SUM") : "SUM";
-  CHECK_(op_ == "SUM") << "only Eltwise SUM is on the hot path (got " << op_
-                       << ")";
+  // SUM is the hot path (the ResNet add) and the only operation with GPU
+  // kernels; PROD runs in CPU mode and is an error in GPU mode, never a
+  // fall-back; MAX is not built
+  CHECK_(op_ == "SUM" || op_ == "PROD")
+      << "Eltwise takes SUM or PROD (got " << op_ << ")";
+  CHECK_(op_ == "SUM" || Engine::get().mode == Mode::CPU)
+      << "only Eltwise SUM is on the hot path: " << op_
+      << " has no GPU kernel";
   coeffs_.assign(bottom.size(), 1.f);
   if (ep) {
     auto cs = ep->nums("coeff");
+    // reference eltwise_layer.cpp LayerSetUp
+    CHECK_(op_ == "SUM" || cs.empty())
+        << "Eltwise layer only takes coefficients for summation.";
     for (size_t i = 0; i < cs.size() && i < coeffs_.size(); ++i)
       coeffs_[i] = (float)cs[i];
   }
@@ -766,6 +775,14 @@ void EltwiseLayer::Forward_cpu(const std::vector<Blob*>& bottom,
                                const std::vector<Blob*>& top) {
   const long n = top[0]->count();
   float* y = top[0]->mutable_cpu_data();
+  if (op_ == "PROD") {
+    memcpy(y, bottom[0]->cpu_data(), sizeof(float) * n);
+    for (size_t i = 1; i < bottom.size(); ++i) {
+      const float* x = bottom[i]->cpu_data();
+      for (long j = 0; j < n; ++j) y[j] *= x[j];
+    }
+    return;
+  }
   memset(y, 0, sizeof(float) * n);
   for (size_t i = 0; i < bottom.size(); ++i)
     cpu::axpy(n, coeffs_[i], bottom[i]->cpu_data(), y);
@@ -779,7 +796,16 @@ void EltwiseLayer::Backward_cpu(const std::vector<Blob*>& top,
   for (size_t i = 0; i < bottom.size(); ++i) {
     if (!prop_down[i]) continue;
     float* dx = bottom[i]->mutable_cpu_diff();
-    if (coeffs_[i] == 1.f)
+    if (op_ == "PROD") {
+      // dy times the product of the other bottoms (the reference's
+      // stable_prod_grad form: no division by a bottom that may be 0)
+      memcpy(dx, dy, sizeof(float) * n);
+      for (size_t k = 0; k < bottom.size(); ++k) {
+        if (k == i) continue;
+        const float* x = bottom[k]->cpu_data();
+        for (long j = 0; j < n; ++j) dx[j] *= x[j];
+      }
+    } else if (coeffs_[i] == 1.f)
       memcpy(dx, dy, sizeof(float) * n);
     else
       for (long j = 0; j < n; ++j) dx[j] = coeffs_[i] * dy[j];

@@ -479,11 +479,12 @@ void EltwiseLayer::Forward_gpu(const std::vector<Blob*>& bottom,
   Engine& E = Engine::get();
   const long n = top[0]->count();
   float* y = top[0]->mutable_gpu_data();
-  if (bottom.size() == 2 && coeffs_[0] == 1.f && coeffs_[1] == 1.f) {
+  if (bottom.size() == 2 && unit_sum()) {
     gpu::add3(E.stream, n, bottom[0]->gpu_data(), bottom[1]->gpu_data(), y,
               fuse_relu_);
     return;
   }
+  CHECK_(op_ == "SUM") << "Eltwise " << op_ << " has no GPU kernel";
   gpu::set_const(E.stream, n, 0.f, y);
   for (size_t i = 0; i < bottom.size(); ++i)
     gpu::axpby(E.stream, n, coeffs_[i], bottom[i]->gpu_data(), 1.f, y);
@@ -494,9 +495,7 @@ void EltwiseLayer::Backward_gpu(const std::vector<Blob*>& top,
                                 const std::vector<Blob*>& bottom) {
   Engine& E = Engine::get();
   const long n = top[0]->count();
-  bool all_one = true;
-  for (float c : coeffs_) all_one = all_one && c == 1.f;
-  if (all_one) {
+  if (unit_sum()) {
     // dx_i == dy exactly: alias the diffs instead of copying (zero kernels;
     // safe because each bottom's diff is consumed before anything rewrites
     // the shared buffer — backward runs top-down on one stream)
@@ -504,6 +503,7 @@ void EltwiseLayer::Backward_gpu(const std::vector<Blob*>& top,
       if (prop_down[i]) bottom[i]->ShareDiff(*top[0]);
     return;
   }
+  CHECK_(op_ == "SUM") << "Eltwise " << op_ << " has no GPU kernel";
   const float* dy = top[0]->gpu_diff();
   for (size_t i = 0; i < bottom.size(); ++i) {
     if (!prop_down[i]) continue;

@@ -1,7 +1,6 @@
 #include "net.hpp"
 
 #include <chrono>
-#include <set>
 
 namespace camd {
 
@@ -50,6 +49,25 @@ Net::Net(const PMsgPtr& net_param, const NetState& state, int batch_override)
   init(net_param, batch_override);
 }
 
+namespace {
+// the Split layer that gives each of `n` consumers of `blob` its own top
+PMsgPtr split_msg(const std::string& blob, const std::string& producer,
+                  int n) {
+  auto sp = std::make_shared<PMsg>();
+  auto addf = [&](const std::string& name, const std::string& v) {
+    PVal pv;
+    pv.kind = PVal::SCALAR;
+    pv.scalar = v;
+    sp->fields.emplace_back(name, pv);
+  };
+  addf("name", blob + "_" + producer + "_split");
+  addf("type", "Split");
+  addf("bottom", blob);
+  for (int c = 0; c < n; ++c) addf("top", blob + "_split_" + std::to_string(c));
+  return sp;
+}
+}  // namespace
+
 // reference src/caffe/util/insert_splits.cpp behaviour: any blob consumed by
 // more than one layer below its producer gets a Split layer so every
 // consumer owns a private diff that Split's backward sums.
@@ -94,19 +112,7 @@ void Net::insert_splits(std::vector<PMsgPtr>& msgs) {
       last_producer[t] = (int)i;
       const std::string k = t + "#" + std::to_string(i);
       if (consumers[k] > 1) {
-        auto sp = std::make_shared<PMsg>();
-        auto addf = [&](const std::string& n, const std::string& v) {
-          PVal pv;
-          pv.kind = PVal::SCALAR;
-          pv.scalar = v;
-          sp->fields.emplace_back(n, pv);
-        };
-        addf("name", t + "_" + m->str("name") + "_split");
-        addf("type", "Split");
-        addf("bottom", t);
-        for (int c = 0; c < consumers[k]; ++c)
-          addf("top", t + "_split_" + std::to_string(c));
-        out.push_back(sp);
+        out.push_back(split_msg(t, m->str("name"), consumers[k]));
         split_base[k] = t;
         split_next[k] = 0;
       }
@@ -115,10 +121,30 @@ void Net::insert_splits(std::vector<PMsgPtr>& msgs) {
   msgs = std::move(out);
 }
 
+namespace {
+// "layer 'conv1' (Convolution) Forward" around one dispatch into layer code
+struct LayerScope : ErrorScope {
+  LayerScope(Layer& l, const char* stage)
+      : ErrorScope("layer '" + l.name() + "' (" + l.type() + ") " + stage) {}
+};
+}  // namespace
+
 void Net::init(const PMsgPtr& msg, int batch_override) {
   name_ = msg->str("name");
+  for (auto& lm : filter_layers(*msg)) append_layer(lm, batch_override);
+  set_backward_flags(msg->boolean("force_backward", false));
+  collect_params();
+  fusions_ = plan_fusions();
+  if (Engine::get().mode == Mode::GPU) {
+    apply_fusions();
+    setup_arena();
+  }
+}
+
+// the layers of this net's state, with Splits inserted
+std::vector<PMsgPtr> Net::filter_layers(const PMsg& msg) {
   std::vector<PMsgPtr> lmsgs;
-  for (auto& lm : msg->subs("layer"))
+  for (auto& lm : msg.subs("layer"))
     if (layer_in_state(*lm, state_)) {
       // shallow-clone: insert_splits rewrites bottom names in place, and
       // the source tree is shared with other nets (train/test pair)
@@ -127,65 +153,65 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
     }
   CHECK_(!lmsgs.empty()) << "net has no layers for this phase";
   insert_splits(lmsgs);
+  return lmsgs;
+}
 
-  for (auto& lm : lmsgs) {
-    auto layer = create_layer(lm);
-    layer->set_phase(phase_);
-    // wire bottoms
-    std::vector<Blob*> bottom, top;
-    for (auto& b : lm->strs("bottom")) {
-      auto it = blob_map_.find(b);
-      CHECK_(it != blob_map_.end())
-          << "layer " << layer->name() << ": unknown bottom blob " << b;
-      bottom.push_back(it->second.get());
+// create one layer, wire it to the blob map and set it up
+void Net::append_layer(const PMsgPtr& lm, int batch_override) {
+  auto layer = create_layer(lm);
+  layer->set_phase(phase_);
+  // wire bottoms
+  std::vector<Blob*> bottom, top;
+  for (auto& b : lm->strs("bottom")) {
+    auto it = blob_map_.find(b);
+    CHECK_(it != blob_map_.end())
+        << "layer " << layer->name() << ": unknown bottom blob " << b;
+    bottom.push_back(it->second.get());
+  }
+  for (auto& t : lm->strs("top")) {
+    auto it = blob_map_.find(t);
+    if (it != blob_map_.end()) {
+      // in-place: top name equals an existing blob (must be a bottom).
+      // A layer WITHOUT bottoms cannot be in-place: its top would
+      // overwrite another layer's (reference net.cpp AppendTop) — two
+      // staged Data layers that the net state did not tell apart
+      CHECK_(!lm->strs("bottom").empty())
+          << "layer '" << layer->name() << "': top blob '" << t
+          << "' is produced by more than one layer (do its include "
+             "rules need a stage or level of the net state?)";
+      top.push_back(it->second.get());
+    } else {
+      auto nb = std::make_shared<Blob>();
+      blob_map_[t] = nb;
+      top.push_back(nb.get());
     }
-    for (auto& t : lm->strs("top")) {
-      auto it = blob_map_.find(t);
-      if (it != blob_map_.end()) {
-        // in-place: top name equals an existing blob (must be a bottom).
-        // A layer WITHOUT bottoms cannot be in-place: its top would
-        // overwrite another layer's (reference net.cpp AppendTop) — two
-        // staged Data layers that the net state did not tell apart
-        CHECK_(!lm->strs("bottom").empty())
-            << "layer '" << layer->name() << "': top blob '" << t
-            << "' is produced by more than one layer (do its include "
-               "rules need a stage or level of the net state?)";
-        top.push_back(it->second.get());
-      } else {
-        auto nb = std::make_shared<Blob>();
-        blob_map_[t] = nb;
-        top.push_back(nb.get());
-      }
-    }
-    const std::string ctx_s =
-        "layer '" + layer->name() + "' (" + layer->type() + ") SetUp";
-    error_context() = ctx_s.c_str();
+  }
+  {
+    LayerScope scope(*layer, "SetUp");
+    layer->SetUp(bottom, top);
     if (batch_override > 0 && layer->type() == "Data") {
       // per-rank batch override (reference divides the prototxt batch
       // across GPUs, parallel.cpp:284-348)
-      layer->SetUp(bottom, top);
       static_cast<DataLayer*>(layer.get())->batch_ = batch_override;
       layer->Reshape(bottom, top);
-    } else {
-      layer->SetUp(bottom, top);
     }
-    error_context() = nullptr;
-    // loss weights
-    auto lw = lm->nums("loss_weight");
-    for (size_t i = 0; i < top.size(); ++i) {
-      float w = i < lw.size() ? (float)lw[i]
-                              : (i == 0 ? layer->default_loss_weight() : 0.f);
-      layer->set_loss((int)i, w);
-    }
-    layers_.push_back(layer);
-    bottoms_.push_back(bottom);
-    tops_.push_back(top);
-    top_names_.push_back(lm->strs("top"));
   }
+  // loss weights
+  auto lw = lm->nums("loss_weight");
+  for (size_t i = 0; i < top.size(); ++i) {
+    float w = i < lw.size() ? (float)lw[i]
+                            : (i == 0 ? layer->default_loss_weight() : 0.f);
+    layer->set_loss((int)i, w);
+  }
+  layers_.push_back(layer);
+  bottoms_.push_back(bottom);
+  tops_.push_back(top);
+  top_names_.push_back(lm->strs("top"));
+}
 
-  // need-backward / propagate-down flags (net.cpp Init bottom-up logic;
-  // force_backward marks every non-data path like the reference does)
-  const bool force = msg->boolean("force_backward", false);
+// need-backward / propagate-down flags (net.cpp Init bottom-up logic;
+// force_backward marks every non-data path like the reference does)
+void Net::set_backward_flags(bool force) {
   std::map<Blob*, bool> blob_needs;
   layer_need_bwd_.resize(layers_.size(), false);
   prop_down_.resize(layers_.size());
@@ -224,8 +250,10 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
       blob_needs[t] =
           need || (force && !is_source && !layers_[i]->is_loss_layer());
   }
+}
 
-  // learnable params in backward-completion order (reverse layer order)
+// learnable params in backward-completion order (reverse layer order)
+void Net::collect_params() {
   for (int i = (int)layers_.size() - 1; i >= 0; --i) {
     auto& lb = layers_[i]->blobs();
     for (size_t j = 0; j < lb.size(); ++j) {
@@ -242,97 +270,110 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
       params_.push_back(p);
     }
   }
-  // GPU-mode forward fusion: an in-place slope-0 ReLU directly after a
-  // BatchNorm or Eltwise(SUM) is applied in the producer's epilogue; the
-  // ReLU layer keeps its backward (it reads its own output, which the
-  // fused producer already wrote post-activation)
-  if (Engine::get().mode == Mode::GPU) {
-    for (size_t i = 1; i < layers_.size(); ++i) {
-      auto* relu = dynamic_cast<ReLULayer*>(layers_[i].get());
-      if (!relu) continue;
-      if (bottoms_[i].size() != 1 || tops_[i].size() != 1) continue;
-      if (bottoms_[i][0] != tops_[i][0]) continue;  // must be in-place
-      auto rp = layers_[i]->param()->sub("relu_param");
-      if (rp && rp->num("negative_slope", 0) != 0) continue;
-      // producer = previous layer producing this blob
-      if (tops_[i - 1].size() != 1 || tops_[i - 1][0] != bottoms_[i][0])
-        continue;
-      if (auto* bn = dynamic_cast<BatchNormLayer*>(layers_[i - 1].get())) {
-        bn->fuse_relu_ = true;
-        relu->fused_away_ = true;
+}
+
+// ------------------------------------------------------------ fusion plan
+bool Net::slope0_relu(int i) const {
+  if (!dynamic_cast<ReLULayer*>(layers_[i].get())) return false;
+  if (bottoms_[i].size() != 1 || tops_[i].size() != 1) return false;
+  auto rp = layers_[i]->param()->sub("relu_param");
+  return !rp || rp->num("negative_slope", 0) == 0;
+}
+
+bool Net::unit_sum2(int i) const {
+  auto* el = dynamic_cast<EltwiseLayer*>(layers_[i].get());
+  return el && bottoms_[i].size() == 2 && el->unit_sum();
+}
+
+// Which producers absorb which followers.  First every in-place slope-0
+// ReLU directly after the BatchNorm, Convolution or unit SUM that produced
+// its blob: the producer applies it in its epilogue (a BN also masks dy in
+// its backward; after a conv or a sum the ReLU keeps its backward, which
+// reads its own output).  Then, TRAIN only (the TEST BN path has no
+// epilogue), the residual add: a unit SUM whose operand comes from the
+// out-of-place BatchNorm immediately before it, that operand having no
+// other consumer — the BN's norm epilogue writes bn(x)+other straight into
+// the sum's top (the ResNet block pattern; kills one full read-add-write
+// pass over the activation per block).  It takes the sum's in-place ReLU
+// along, or absorbs an out-of-place slope-0 ReLU that is the sum's only
+// consumer: the sum is then never materialized and that ReLU's backward
+// masks by its top's sign instead.
+std::vector<Net::Fusion> Net::plan_fusions() const {
+  const int L = (int)layers_.size();
+  std::map<const Blob*, int> consumers;
+  for (auto& bs : bottoms_)
+    for (auto* b : bs) ++consumers[b];
+  std::vector<Fusion> plan;
+  std::vector<int> made(L, -1);  // the kind layer i produces, or -1
+  auto add = [&](Fusion::Kind k, int producer, std::vector<int> absorbed,
+                 bool relu) {
+    made[producer] = k;
+    plan.push_back({k, producer, std::move(absorbed), relu});
+  };
+  for (int i = 1; i < L; ++i) {
+    if (!slope0_relu(i) || !in_place(i)) continue;
+    if (!fed_by_previous(i, bottoms_[i][0])) continue;
+    Layer* prev = layers_[i - 1].get();
+    if (dynamic_cast<BatchNormLayer*>(prev))
+      add(Fusion::BN_RELU, i - 1, {i}, true);
+    else if (dynamic_cast<ConvolutionLayer*>(prev))
+      add(Fusion::CONV_RELU, i - 1, {i}, true);  // GemmEpi.relu
+    else if (unit_sum2(i - 1))
+      add(Fusion::SUM_RELU, i - 1, {i}, true);
+  }
+  for (int i = 1; i < L && phase_ == Phase::TRAIN; ++i) {
+    if (!unit_sum2(i)) continue;
+    if (!dynamic_cast<BatchNormLayer*>(layers_[i - 1].get())) continue;
+    if (made[i - 1] != -1) continue;  // fused with a ReLU or another add
+    if (!fed_by_previous(i, bottoms_[i][0]) &&
+        !fed_by_previous(i, bottoms_[i][1]))
+      continue;
+    if (in_place(i - 1) || consumers[tops_[i - 1][0]] != 1) continue;
+    const Blob* sum = tops_[i][0];
+    if (i + 1 < L && slope0_relu(i + 1) && !in_place(i + 1) &&
+        bottoms_[i + 1][0] == sum && consumers[sum] == 1)
+      add(Fusion::BN_ADD_RELU, i - 1, {i, i + 1}, true);
+    else
+      add(Fusion::BN_ADD, i - 1, {i}, made[i] == Fusion::SUM_RELU);
+  }
+  std::stable_sort(plan.begin(), plan.end(),
+                   [](const Fusion& a, const Fusion& b) {
+                     return a.producer < b.producer;
+                   });
+  return plan;
+}
+
+// set the layer flags the GPU paths read (layers.hpp)
+void Net::apply_fusions() {
+  for (auto& f : fusions_) {
+    Layer* p = layers_[f.producer].get();
+    const int a = f.absorbed[0];
+    // the absorbed ReLU; none in a BN_ADD, whose last absorbed is the sum
+    auto* relu = dynamic_cast<ReLULayer*>(layers_[f.absorbed.back()].get());
+    if (relu) relu->fused_away_ = true;
+    switch (f.kind) {
+      case Fusion::BN_RELU:
+        static_cast<BatchNormLayer*>(p)->fuse_relu_ = true;
         relu->bwd_fused_ = true;  // BN backward masks dy by the activation
-      } else if (auto* cv =
-                     dynamic_cast<ConvolutionLayer*>(layers_[i - 1].get())) {
-        cv->fuse_relu_ = true;  // GemmEpi.relu (AlexNet/GoogLeNet pattern)
-        relu->fused_away_ = true;
-      } else if (auto* el =
-                     dynamic_cast<EltwiseLayer*>(layers_[i - 1].get())) {
-        bool ones = el->op_ == "SUM";
-        for (float c : el->coeffs_) ones = ones && c == 1.f;
-        if (ones && bottoms_[i - 1].size() == 2) {
-          el->fuse_relu_ = true;
-          relu->fused_away_ = true;
-        }
+        break;
+      case Fusion::CONV_RELU:
+        static_cast<ConvolutionLayer*>(p)->fuse_relu_ = true;
+        break;
+      case Fusion::SUM_RELU:
+        static_cast<EltwiseLayer*>(p)->fuse_relu_ = true;
+        break;
+      case Fusion::BN_ADD_RELU:
+        relu->bwd_from_top_ = true;
+        [[fallthrough]];
+      case Fusion::BN_ADD: {
+        auto* bn = static_cast<BatchNormLayer*>(p);
+        bn->fuse_add_other_ =
+            bottoms_[a][tops_[f.producer][0] == bottoms_[a][0] ? 1 : 0];
+        bn->fuse_add_out_ = tops_[f.absorbed.back()][0];
+        bn->fuse_add_relu_ = f.relu;
+        static_cast<EltwiseLayer*>(layers_[a].get())->fused_away_ = true;
       }
     }
-    // residual-add fusion (TRAIN only; the TEST BN path has no epilogue):
-    // Eltwise(SUM, coeffs 1) whose first-hand operand is produced by the
-    // immediately preceding BatchNorm, and that operand has no other
-    // consumer — the BN's norm epilogue writes bn(x)+other straight into
-    // the sum's top (the ResNet block pattern; kills one full
-    // read-add-write pass over the activation per block)
-    if (phase_ == Phase::TRAIN) {
-      for (size_t i = 1; i < layers_.size(); ++i) {
-        auto* el = dynamic_cast<EltwiseLayer*>(layers_[i].get());
-        if (!el || el->fused_away_) continue;
-        if (el->op_ != "SUM" || bottoms_[i].size() != 2) continue;
-        bool ones = true;
-        for (float c : el->coeffs_) ones = ones && c == 1.f;
-        if (!ones) continue;
-        auto* bn = dynamic_cast<BatchNormLayer*>(layers_[i - 1].get());
-        if (!bn || bn->fuse_relu_ || bn->fuse_add_out_) continue;
-        if (tops_[i - 1].size() != 1) continue;
-        Blob* bnout = tops_[i - 1][0];
-        if (bnout == bottoms_[i - 1][0]) continue;  // in-place BN: keep
-        int idx = bnout == bottoms_[i][0] ? 0
-                  : bnout == bottoms_[i][1] ? 1
-                                            : -1;
-        if (idx < 0) continue;
-        int consumers = 0;
-        for (size_t k = 0; k < layers_.size(); ++k)
-          for (auto* b : bottoms_[k]) consumers += b == bnout;
-        if (consumers != 1) continue;
-        bn->fuse_add_other_ = bottoms_[i][1 - idx];
-        bn->fuse_add_out_ = tops_[i][0];
-        bn->fuse_add_relu_ = el->fuse_relu_;
-        el->fused_away_ = true;
-        // absorb a following non-in-place slope-0 ReLU too: the epilogue
-        // writes relu(bn(x)+other) straight into the ReLU's top and the
-        // sum is never materialized (its only consumer is the ReLU, whose
-        // backward masks by the top's sign instead)
-        if (i + 1 < layers_.size()) {
-          auto* relu = dynamic_cast<ReLULayer*>(layers_[i + 1].get());
-          if (relu && !relu->fused_away_ && bottoms_[i + 1].size() == 1 &&
-              tops_[i + 1].size() == 1 &&
-              bottoms_[i + 1][0] == tops_[i][0] &&
-              bottoms_[i + 1][0] != tops_[i + 1][0]) {
-            auto rp = relu->param()->sub("relu_param");
-            const bool slope0 = !rp || rp->num("negative_slope", 0) == 0;
-            Blob* sum = tops_[i][0];
-            int sum_consumers = 0;
-            for (size_t k = 0; k < layers_.size(); ++k)
-              for (auto* b : bottoms_[k]) sum_consumers += b == sum;
-            if (slope0 && sum_consumers == 1) {
-              bn->fuse_add_out_ = tops_[i + 1][0];
-              bn->fuse_add_relu_ = true;
-              relu->fused_away_ = true;
-              relu->bwd_from_top_ = true;
-            }
-          }
-        }
-      }
-    }
-    setup_arena();
   }
 }
 
@@ -350,15 +391,18 @@ void Net::setup_arena() {
     HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
 }
 
+void Net::forward_layer(size_t i) {
+  LayerScope scope(*layers_[i], "Forward");
+  layers_[i]->Forward(bottoms_[i], tops_[i]);
+}
+
+void Net::backward_layer(size_t i) {
+  LayerScope scope(*layers_[i], "Backward");
+  layers_[i]->Backward(tops_[i], prop_down_[i], bottoms_[i]);
+}
+
 void Net::Forward() {
-  for (size_t i = 0; i < layers_.size(); ++i)
-    {
-      const std::string ctx_s = "layer '" + layers_[i]->name() + "' (" +
-                                layers_[i]->type() + ") Forward";
-      error_context() = ctx_s.c_str();
-      layers_[i]->Forward(bottoms_[i], tops_[i]);
-      error_context() = nullptr;
-    }
+  for (size_t i = 0; i < layers_.size(); ++i) forward_layer(i);
 }
 
 void Net::Backward(ReduceHook* hook) {
@@ -367,14 +411,7 @@ void Net::Backward(ReduceHook* hook) {
   size_t pidx = 0;
   hipEvent_t last_ev = nullptr;
   for (int i = (int)layers_.size() - 1; i >= 0; --i) {
-    if (layer_need_bwd_[i])
-      {
-        const std::string ctx_s = "layer '" + layers_[i]->name() + "' (" +
-                                  layers_[i]->type() + ") Backward";
-        error_context() = ctx_s.c_str();
-        layers_[i]->Backward(tops_[i], prop_down_[i], bottoms_[i]);
-        error_context() = nullptr;
-      }
+    if (layer_need_bwd_[i]) backward_layer(i);
     if (hook) {
       // emit this layer's params (consecutive in params_, ascending offset)
       const size_t start = pidx;
@@ -499,15 +536,7 @@ void Net::SaveWeights(const std::string& path) {
     wire::Writer lw;
     lw.str(1, layers_[i]->name());
     lw.str(2, layers_[i]->type());
-    for (auto& b : lb) {
-      wire::Writer bw;
-      bw.packed_floats(5, b->cpu_data(), b->count());
-      wire::Writer sw;
-      std::vector<int64_t> dims(b->shape().begin(), b->shape().end());
-      sw.packed_i64(1, dims);
-      bw.submsg(7, sw.out);
-      lw.submsg(7, bw.out);
-    }
+    for (auto& b : lb) lw.blob(7, b->cpu_data(), b->count(), b->shape());
     net_w.submsg(100, lw.out);
   }
   const auto dir = std::filesystem::path(path).parent_path();
@@ -566,26 +595,14 @@ void Net::time_layers(int iters) {
   for (int it = 0; it < iters; ++it) {
     for (size_t i = 0; i < L; ++i) {
       auto t0 = tick();
-      {
-      const std::string ctx_s = "layer '" + layers_[i]->name() + "' (" +
-                                layers_[i]->type() + ") Forward";
-      error_context() = ctx_s.c_str();
-      layers_[i]->Forward(bottoms_[i], tops_[i]);
-      error_context() = nullptr;
-    }
+      forward_layer(i);
       auto t1 = tick();
       fwd_ms[i] += std::chrono::duration<double, std::milli>(t1 - t0).count();
     }
     for (size_t i = L; i-- > 0;) {
       if (!layer_need_bwd_[i]) continue;
       auto t0 = tick();
-      {
-        const std::string ctx_s = "layer '" + layers_[i]->name() + "' (" +
-                                  layers_[i]->type() + ") Backward";
-        error_context() = ctx_s.c_str();
-        layers_[i]->Backward(tops_[i], prop_down_[i], bottoms_[i]);
-        error_context() = nullptr;
-      }
+      backward_layer(i);
       auto t1 = tick();
       bwd_ms[i] += std::chrono::duration<double, std::milli>(t1 - t0).count();
     }

@@ -115,10 +115,53 @@ class Net {
   // `caffe time`-style per-layer forward/backward timing report
   void time_layers(int iters);
 
+  // One producer layer absorbing the work of the layer(s) after it.  The
+  // plan is a function of the built graph alone and is made in both modes;
+  // only GPU mode applies it (no CPU layer path fuses).
+  struct Fusion {
+    enum Kind {
+      BN_RELU,      // BN + in-place ReLU: forward and backward absorbed
+      CONV_RELU,    // Conv + in-place ReLU: forward only
+      SUM_RELU,     // Eltwise SUM + in-place ReLU: forward only
+      BN_ADD,       // BN + residual add (TRAIN): the BN writes the sum's top
+      BN_ADD_RELU,  // ... and a following out-of-place ReLU, which then
+                    // masks its backward by its own top
+    };
+    Kind kind;
+    int producer;               // layer index
+    std::vector<int> absorbed;  // layer indices, in layer order
+    // the producer's epilogue applies a ReLU: always, but for a BN_ADD only
+    // when the sum has an in-place ReLU (their own SUM_RELU entry) to take
+    // along
+    bool relu;
+  };
+  // in layer order of the producers
+  const std::vector<Fusion>& fusions() const { return fusions_; }
+
  private:
+  // the net build, in order; each step reads and writes the members below
   void init(const PMsgPtr& msg, int batch_override);
+  std::vector<PMsgPtr> filter_layers(const PMsg& msg);
   void insert_splits(std::vector<PMsgPtr>& layer_msgs);
+  void append_layer(const PMsgPtr& layer_msg, int batch_override);
+  void set_backward_flags(bool force_backward);
+  void collect_params();
+  std::vector<Fusion> plan_fusions() const;
+  void apply_fusions();
   void setup_arena();
+
+  // the graph predicates the fusion plan is made of
+  bool in_place(int i) const { return bottoms_[i][0] == tops_[i][0]; }
+  bool slope0_relu(int i) const;  // one-bottom one-top ReLU, slope 0
+  bool unit_sum2(int i) const;    // Eltwise SUM of two bottoms, coeffs 1
+  // layer i-1 has one top and that top is `blob`
+  bool fed_by_previous(int i, const Blob* blob) const {
+    return i >= 1 && tops_[i - 1].size() == 1 && tops_[i - 1][0] == blob;
+  }
+
+  // one layer's dispatch under its error scope
+  void forward_layer(size_t i);
+  void backward_layer(size_t i);
 
   std::string name_;
   Phase phase_;
@@ -130,6 +173,7 @@ class Net {
   std::vector<bool> layer_need_bwd_;
   std::map<std::string, std::shared_ptr<Blob>> blob_map_;
   std::vector<LParam> params_;
+  std::vector<Fusion> fusions_;
   long arena_count_ = 0;
   float* diff_arena_ = nullptr;
   std::vector<hipEvent_t> layer_events_;

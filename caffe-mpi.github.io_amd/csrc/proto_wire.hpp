@@ -56,6 +56,14 @@ class Writer {
     varint(bytes.size());
     out += bytes;
   }
+  // a BlobProto submessage: data=5 (packed float), shape=7 (BlobShape)
+  void blob(int field, const float* p, long n, const std::vector<int>& shape) {
+    Writer bw, sw;
+    bw.packed_floats(5, p, n);
+    sw.packed_i64(1, std::vector<int64_t>(shape.begin(), shape.end()));
+    bw.submsg(7, sw.out);
+    submsg(field, bw.out);
+  }
 };
 
 // ------------------------------------------------------------- reader

@@ -17,8 +17,7 @@ const char* const kTypeNames[kNumSolverRules] = {
 const char* const kEnumNames[kNumSolverRules] = {
     "SGD", "NESTEROV", "ADAGRAD", "RMSPROP", "ADADELTA", "ADAM"};
 
-// CPU-mode update of one param for every rule but SGD+L2 (whose loop stays
-// in Reducer::flush): the per-element rule the GPU kernel runs
+// CPU-mode update of one param: the per-element rule the GPU kernels run
 template <int Rule, bool kL1>
 void cpu_rule_loop(long n, float* g, float* w, float* h, float* h2,
                    const SolverCoef& c, float lr, float decay) {
@@ -134,40 +133,51 @@ Solver::Solver(const PMsgPtr& sp, int batch_override) : param_(sp) {
   parse_states();
   net_.reset(new Net(net_msg, train_state_, batch_override));
   weight_decay_ = (float)sp->num("weight_decay", 0.0);
-  const long nparams = (long)net_->learnable_params().size();
   const long buckets = sp->inum("reduce_buckets", 6);  // caffe.proto:140
   bucket_budget_ =
       std::max<long>(1, net_->learnable_count() / std::max<long>(1, buckets));
-  if (E.mode == Mode::GPU && net_->learnable_count() > 0) {
-    history_ =
-        (float*)E.dalloc.alloc(sizeof(float) * net_->learnable_count());
-    HIP_CHECK(hipMemsetAsync(history_, 0,
-                             sizeof(float) * net_->learnable_count(),
-                             E.stream));
-    if (history_slots() == 2) {
-      history2_ =
-          (float*)E.dalloc.alloc(sizeof(float) * net_->learnable_count());
-      HIP_CHECK(hipMemsetAsync(history2_, 0,
-                               sizeof(float) * net_->learnable_count(),
-                               E.stream));
-    }
-  } else if (nparams > 0) {
-    host_history_.assign(net_->learnable_count(), 0.f);
-    if (history_slots() == 2)
-      host_history2_.assign(net_->learnable_count(), 0.f);
+  for (int slot = 0; slot < history_slots(); ++slot)
+    history_[slot].alloc(net_->learnable_count());
+}
+
+void StateBuf::alloc(long count) {
+  Engine& E = Engine::get();
+  count_ = count;
+  if (count == 0) return;
+  if (E.mode == Mode::GPU) {
+    dev_ = (float*)E.dalloc.alloc(sizeof(float) * count);
+    zero();
+  } else {
+    host_.assign(count, 0.f);
   }
 }
 
-Solver::~Solver() {
-  if (history_)
-    Engine::get().dalloc.release(history_,
-                                 sizeof(float) * net_->learnable_count());
-  if (history2_)
-    Engine::get().dalloc.release(history2_,
-                                 sizeof(float) * net_->learnable_count());
-  if (acc_)
-    Engine::get().dalloc.release(acc_,
-                                 sizeof(float) * net_->learnable_count());
+StateBuf::~StateBuf() {
+  if (dev_) Engine::get().dalloc.release(dev_, sizeof(float) * count_);
+}
+
+void StateBuf::zero() {
+  if (dev_)
+    HIP_CHECK(hipMemsetAsync(dev_, 0, sizeof(float) * count_,
+                             Engine::get().stream));
+  else
+    std::fill(host_.begin(), host_.end(), 0.f);
+}
+
+void StateBuf::read(long offset, long count, float* out) {
+  if (dev_)
+    HIP_CHECK(hipMemcpy(out, dev_ + offset, sizeof(float) * count,
+                        hipMemcpyDeviceToHost));
+  else
+    memcpy(out, host_.data() + offset, sizeof(float) * count);
+}
+
+void StateBuf::write(long offset, const float* in, long count) {
+  if (dev_)
+    HIP_CHECK(hipMemcpy(dev_ + offset, in, sizeof(float) * count,
+                        hipMemcpyHostToDevice));
+  else
+    memcpy(host_.data() + offset, in, sizeof(float) * count);
 }
 
 // acc += diff (merge_back=false, after each non-final sub-pass) or
@@ -175,29 +185,25 @@ Solver::~Solver() {
 void Solver::accumulate_diffs(bool merge_back) {
   Engine& E = Engine::get();
   const long total = net_->learnable_count();
+  if (acc_.empty()) acc_.alloc(total);
   if (E.mode == Mode::GPU) {
-    if (!acc_) {
-      acc_ = (float*)E.dalloc.alloc(sizeof(float) * total);
-      HIP_CHECK(hipMemsetAsync(acc_, 0, sizeof(float) * total, E.stream));
-    }
-    if (!merge_back) {
-      gpu::axpy(E.stream, total, 1.f, net_->diff_arena(), acc_);
-    } else {
-      gpu::axpy(E.stream, total, 1.f, acc_, net_->diff_arena());
-      HIP_CHECK(hipMemsetAsync(acc_, 0, sizeof(float) * total, E.stream));
-    }
+    // the device diffs are one arena
+    if (!merge_back)
+      gpu::axpy(E.stream, total, 1.f, net_->diff_arena(), acc_.ptr());
+    else
+      gpu::axpy(E.stream, total, 1.f, acc_.ptr(), net_->diff_arena());
   } else {
-    if (host_acc_.empty()) host_acc_.assign(total, 0.f);
+    // the host diffs are per blob
     for (auto& p : net_->learnable_params()) {
       float* diff = p.blob->mutable_cpu_diff();
-      float* acc = host_acc_.data() + p.offset;
+      float* acc = acc_.ptr() + p.offset;
       if (!merge_back)
         cpu::axpy(p.count, 1.f, diff, acc);
       else
         cpu::axpy(p.count, 1.f, acc, diff);
     }
-    if (merge_back) std::fill(host_acc_.begin(), host_acc_.end(), 0.f);
   }
+  if (merge_back) acc_.zero();
 }
 
 float Solver::GetLearningRate() const {
@@ -346,23 +352,10 @@ void Reducer::flush(hipEvent_t ev) {
       const auto& p = params[k];
       float* g = p.blob->mutable_cpu_diff();
       float* w = p.blob->mutable_cpu_data();
-      float* h = S.host_history().data() + p.offset;
-      const float lr = S.cur_lr_ * p.lr_mult;
-      const float decay = S.weight_decay_ * p.decay_mult;
-      if (S.rule_ != kRuleSgd || S.l1_) {
-        float* h2 = S.history_slots() == 2
-                        ? S.host_history(1).data() + p.offset
-                        : nullptr;
-        cpu_rule_update(S.rule_, S.l1_, p.count, g, w, h, h2, S.coef(),
-                        S.upd_lr_ * p.lr_mult, decay);
-        continue;
-      }
-      for (long i = 0; i < p.count; ++i) {
-        float gi = g[i] * S.grad_scale_ + decay * w[i];
-        gi = h[i] = S.cur_mom_ * h[i] + lr * gi;
-        w[i] -= gi;
-        g[i] = 0.f;
-      }
+      float* h = S.history(0) + p.offset;
+      float* h2 = S.history_slots() == 2 ? S.history(1) + p.offset : nullptr;
+      cpu_rule_update(S.rule_, S.l1_, p.count, g, w, h, h2, S.coef(),
+                      S.upd_lr_ * p.lr_mult, S.weight_decay_ * p.decay_mult);
     }
   }
   bucket_start_ = bucket_end_;
@@ -484,14 +477,8 @@ void Solver::copy_history(int slot, int param_index, float* out, long count) {
       << "param index " << param_index;
   const auto& p = params[param_index];
   CHECK_LE_(count, p.count);
-  Engine& E = Engine::get();
-  if (E.mode == Mode::GPU) {
-    E.sync();  // the updates run on comm_stream
-    HIP_CHECK(hipMemcpy(out, history(slot) + p.offset, sizeof(float) * count,
-                        hipMemcpyDeviceToHost));
-  } else {
-    memcpy(out, host_history(slot).data() + p.offset, sizeof(float) * count);
-  }
+  Engine::get().sync();  // the updates run on comm_stream
+  history_[slot].read(p.offset, count, out);
 }
 
 std::shared_ptr<Solver> create_solver_from_file(const std::string& path,
@@ -499,26 +486,20 @@ std::shared_ptr<Solver> create_solver_from_file(const std::string& path,
   return std::make_shared<Solver>(parse_prototxt_file(path), batch_override);
 }
 
+long Solver::train_batch() const {
+  for (auto& l : net_->layers())
+    if (auto* d = dynamic_cast<const DataLayer*>(l.get())) return d->batch_;
+  return 0;
+}
+
 double Solver::perf_img_per_sec() const {
   if (perf_iters_ == 0 || perf_seconds_ <= 0) return 0.0;
-  long batch = 0;
-  for (auto& l : net_->layers())
-    if (auto* d = dynamic_cast<const DataLayer*>(l.get())) {
-      batch = d->batch_;
-      break;
-    }
-  return perf_iters_ / perf_seconds_ * batch;
+  return perf_iters_ / perf_seconds_ * train_batch();
 }
 
 void Solver::print_perf_report() const {
   if (perf_iters_ == 0 || perf_seconds_ <= 0) return;
-  // batch size from the train net's data layer (first layer top 0)
-  long batch = 0;
-  for (auto& l : net_->layers())
-    if (auto* d = dynamic_cast<const DataLayer*>(l.get())) {
-      batch = d->batch_;
-      break;
-    }
+  const long batch = train_batch();
   const double ratio = perf_iters_ / perf_seconds_;
   fprintf(stderr,
           "Solver performance on device %d: %.4g * %ld = %.5g img/sec\n",
@@ -620,7 +601,6 @@ void Solver::Snapshot() {
   net_->SaveWeights(model);
   // SolverState { iter=1, learned_net=2, history=3 (BlobProto),
   // current_step=4 } — caffe.proto:303-308
-  Engine& E = Engine::get();
   wire::Writer sw;
   sw.vint(1, iter_);
   sw.str(2, model);
@@ -634,21 +614,9 @@ void Solver::Snapshot() {
   for (int slot = 0; slot < history_slots(); ++slot)
     for (int pi : net_->forward_param_order()) {
       const auto& p = aparams[pi];
-      wire::Writer bw;
-      if (E.mode == Mode::GPU) {
-        host.resize(p.count);
-        HIP_CHECK(hipMemcpy(host.data(), history(slot) + p.offset,
-                            sizeof(float) * p.count, hipMemcpyDeviceToHost));
-        bw.packed_floats(5, host.data(), p.count);
-      } else {
-        bw.packed_floats(5, host_history(slot).data() + p.offset, p.count);
-      }
-      wire::Writer shw;
-      std::vector<int64_t> dims(p.blob->shape().begin(),
-                                p.blob->shape().end());
-      shw.packed_i64(1, dims);
-      bw.submsg(7, shw.out);
-      sw.submsg(3, bw.out);
+      host.resize(p.count);
+      history_[slot].read(p.offset, p.count, host.data());
+      sw.blob(3, host.data(), p.count, p.blob->shape());
     }
   sw.vint(4, current_step_);
   {
@@ -666,7 +634,6 @@ void Solver::Restore(const std::string& path) {
   CHECK_(f.good()) << "cannot read " << path;
   std::string buf((std::istreambuf_iterator<char>(f)),
                   std::istreambuf_iterator<char>());
-  Engine& E = Engine::get();
   wire::Reader r(buf.data(), buf.size());
   wire::Field fld;
   std::string learned;
@@ -699,14 +666,7 @@ void Solver::Restore(const std::string& path) {
       const int slot = (int)(hidx / nparams);
       const auto& p = params[order[hidx % nparams]];
       CHECK_EQ_((long)b.data.size(), p.count);
-      if (E.mode == Mode::GPU) {
-        HIP_CHECK(hipMemcpy(history(slot) + p.offset, b.data.data(),
-                            sizeof(float) * b.data.size(),
-                            hipMemcpyHostToDevice));
-      } else {
-        memcpy(host_history(slot).data() + p.offset, b.data.data(),
-               sizeof(float) * b.data.size());
-      }
+      history_[slot].write(p.offset, b.data.data(), p.count);
       ++hidx;
     }
   }

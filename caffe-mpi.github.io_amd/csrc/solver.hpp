@@ -41,6 +41,30 @@ std::unique_ptr<Comm> make_callback_comm(HostAllreduceFn fn, void* ud,
 
 class Solver;
 
+// Solver state in diff-arena layout (SGD history, the iter_size
+// accumulator): zero-filled floats that live on the device in GPU mode and
+// in a host vector in CPU mode.  Device memory comes from Engine::dalloc
+// and goes back to it in the destructor, without a HIP call.
+class StateBuf {
+ public:
+  StateBuf() = default;
+  StateBuf(const StateBuf&) = delete;
+  StateBuf& operator=(const StateBuf&) = delete;
+  ~StateBuf();
+  void alloc(long count);  // once; zero-filled on the compute stream
+  bool empty() const { return count_ == 0; }
+  float* ptr() { return dev_ ? dev_ : host_.data(); }  // null while empty
+  // blocking copies out of and into [offset, offset + count)
+  void read(long offset, long count, float* out);
+  void write(long offset, const float* in, long count);
+  void zero();  // on the compute stream
+
+ private:
+  float* dev_ = nullptr;
+  std::vector<float> host_;
+  long count_ = 0;
+};
+
 // reference SolverAction (include/caffe/solver.hpp + util/signal_handler):
 // polled once per iteration inside Step — NONE continue, STOP break out
 // (requested_early_exit_), SNAPSHOT snapshot and continue
@@ -66,7 +90,6 @@ class Reducer : public ReduceHook {
 class Solver {
  public:
   explicit Solver(const PMsgPtr& solver_param, int batch_override = 0);
-  ~Solver();
 
   void Step(int iters);
   float GetLearningRate() const;  // sgd_solver.cpp:24-66 policies + rampup
@@ -115,10 +138,9 @@ class Solver {
 
   void set_comm(std::unique_ptr<Comm> c) { comm_ = std::move(c); }
   Comm* comm() { return comm_.get(); }
-  float* history(int slot = 0) { return slot ? history2_ : history_; }
-  std::vector<float>& host_history(int slot = 0) {
-    return slot ? host_history2_ : host_history_;
-  }
+  // history slot in diff-arena layout, device or host by mode; null for a
+  // slot the rule does not have
+  float* history(int slot = 0) { return history_[slot].ptr(); }
   void bcast_weights();  // initial weight broadcast (parallel.cpp:208-227)
 
   // per-iteration cached coefficients for the fused update
@@ -149,11 +171,8 @@ class Solver {
   bool snapshot_enabled_ = true;
   long iter_ = 0;
   mutable int current_step_ = 0;
-  float* history_ = nullptr;  // device arena, diff-arena layout
-  std::vector<float> host_history_;
-  // second history slot (AdaDelta, Adam only): same layout, zero-filled
-  float* history2_ = nullptr;
-  std::vector<float> host_history2_;
+  // allocated at construction; the second slot by AdaDelta and Adam only
+  StateBuf history_[2];
   // the update rule, parsed once at construction
   int rule_ = kRuleSgd;
   bool l1_ = false;
@@ -172,9 +191,9 @@ class Solver {
   // iter_size accumulation buffer (diff-arena layout; only allocated when
   // iter_size > 1 — layer backwards overwrite their param diffs, so cross-
   // pass accumulation happens here instead of in every wgrad kernel)
-  float* acc_ = nullptr;
-  std::vector<float> host_acc_;
+  StateBuf acc_;
   void accumulate_diffs(bool merge_back);
+  long train_batch() const;  // of the train net's data layer, 0 without one
   // perf-report bookkeeping
   double perf_seconds_ = 0.0;
   long perf_iters_ = 0;

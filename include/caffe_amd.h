@@ -209,6 +209,15 @@ int caffe_gemm_trace_readers(long* cursor, long* wide64);
  * "op=solver_seg rule=adam reg=L2 lo=0 hi=272 nseg=6". */
 int caffe_kernel_trace(int enable);
 int caffe_kernel_trace_read(char* buf, int cap);
+/* The graph fusions planned for a net at build time, same buffer contract
+ * as the _trace_read calls: one line "kind producer absorbed[,absorbed]"
+ * per fusion, in layer order of the producer, the names being layer names.
+ * kind: bn_relu | conv_relu | sum_relu (the producer applies the in-place
+ * ReLU after it) | bn_add (a TRAIN BatchNorm writes the residual sum after
+ * it) | bn_add_relu (and the out-of-place ReLU after that sum).  The plan
+ * depends on the graph alone and is the same in CPU mode, where nothing
+ * is fused. */
+int caffe_net_fusions(caffe_net_t net, char* buf, int cap);
 /* Self-test of the exact fast division the GEMM staging decomposes its view
  * indices with (host code, no GPU): for every divisor in [d_lo, d_hi]
  * compares quotient and remainder with / and % over the dividends 0..2^20,

@@ -44,19 +44,26 @@ def gen_graph(rng):
             cur = f"{top}bn"
         elif kind == "residual":
             co = int(rng.integers(3, 6))
-            lines += [
-                # two branches from cur: conv+BN vs 1x1 conv; SUM; ReLU
+            # two branches from cur: conv+BN vs 1x1 conv; SUM; ReLU
+            branch = [
                 f'layer {{ name: "{nm}a" type: "Convolution" '
                 f'bottom: "{cur}" top: "{top}a" convolution_param {{ '
                 f'num_output: {co} kernel_size: 3 pad: 1 '
                 f'weight_filler {{ type: "gaussian" std: 0.3 }} }} }}',
                 f'layer {{ name: "{nm}ab" type: "BatchNorm" '
                 f'bottom: "{top}a" top: "{top}abn" '
-                f'batch_norm_param {{ scale_bias: true }} }}',
+                f'batch_norm_param {{ scale_bias: true }} }}']
+            shortcut = [
                 f'layer {{ name: "{nm}s" type: "Convolution" '
                 f'bottom: "{cur}" top: "{top}s" convolution_param {{ '
                 f'num_output: {co} kernel_size: 1 bias_term: false '
-                f'weight_filler {{ type: "gaussian" std: 0.3 }} }} }}',
+                f'weight_filler {{ type: "gaussian" std: 0.3 }} }} }}']
+            # shortcut first: the BN sits right before the sum and the
+            # BN + residual-add fusion fires; shortcut second: the conv
+            # between them keeps it from firing
+            lines += (shortcut + branch if rng.integers(0, 2) else
+                      branch + shortcut)
+            lines += [
                 f'layer {{ name: "{nm}e" type: "Eltwise" '
                 f'bottom: "{top}abn" bottom: "{top}s" top: "{top}" '
                 f'eltwise_param {{ operation: SUM }} }}',
@@ -108,8 +115,26 @@ def gen_graph(rng):
     return head + "\n".join(lines), (n, c, hw)
 
 
+SEEDS = [5, 19, 42, 77, 101, 137]
+
+
+def test_fuzz_seeds_plan_every_in_place_fusion():
+    # what the seeds are for: between them the generated graphs fuse a ReLU
+    # into a BN, a conv and a sum, and a residual add into a BN, and one
+    # of them holds a residual block that must not fuse its add
+    ca.set_mode("cpu")
+    kinds, unfused_add = set(), False
+    for seed in SEEDS:
+        text, _ = gen_graph(np.random.default_rng(seed))
+        mine = [k for k, _, _ in net_from_text(text).fusions()]
+        kinds |= set(mine)
+        unfused_add |= mine.count("sum_relu") > mine.count("bn_add")
+    assert kinds == {"bn_relu", "conv_relu", "sum_relu", "bn_add"}
+    assert unfused_add
+
+
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("seed", [5, 19, 42, 77, 101, 137])
+@pytest.mark.parametrize("seed", SEEDS)
 def test_gpu_graph_fusion_parity(seed, dtype):
     # tol: exact-class for f32, the bf16 mixed-precision class otherwise
     tol = 1e-3 if dtype == "f32" else 4e-2
@@ -144,3 +169,82 @@ def test_gpu_graph_fusion_parity(seed, dtype):
     for i, (a, b) in enumerate(zip(pc, pg)):
         s = max(np.abs(a).max(), 1e-3)
         assert np.abs(b - a).max() < tol * s, f"param {i}"
+
+
+# eltwise-class launches (add3, axpby, copy, ... of one forward + backward)
+# of the hand graphs as measured on the parent commit b1ffb37 on the MI355X:
+# the fusion flags moved from two passes in Net::init to a plan, and what
+# the GPU launches for a graph must not have moved with them
+PARENT_ELTWISE_LAUNCHES = {
+    "bn_relu": 0, "conv_relu": 0, "residual": 1, "residual_bn_second": 1,
+    "residual_relu_out": 1, "leaky_relu": 0, "conv_between": 2,
+    "sum_twice": 3,
+}
+
+
+def _hand_graphs():
+    import fusion_graphs as fg
+    # every positive graph, each followed by its nearest negative: the first
+    # one that was derived from it
+    out = []
+    for name, g in fg.POSITIVE.items():
+        out.append((name,) + g)
+        near = [(n,) + v[1:] for n, v in fg.NEGATIVE.items() if v[0] == name]
+        out += near[:1]
+    return out
+
+
+@pytest.mark.parametrize("name,text,phase,expected",
+                         _hand_graphs(), ids=[g[0] for g in _hand_graphs()])
+def test_hand_graph_launches_and_parity(name, text, phase, expected):
+    import fusion_graphs as fg
+    rng = np.random.default_rng(11)
+    x = rng.standard_normal(fg.SHAPE).astype(np.float32)
+    labels = rng.integers(0, 4, fg.SHAPE[0]).astype(np.float32)
+    results = {}
+    for mode in ("cpu", "gpu"):
+        ca.set_mode(mode)
+        ca.set_random_seed(2024)
+        net = net_from_text(text, phase=phase)
+        assert net.fusions() == expected
+        net.set_blob("in0", x)
+        net.set_blob("in1", labels)
+        ca.device_synchronize()
+        ca.perf_reset()
+        net.forward()
+        net.backward()
+        ca.device_synchronize()
+        perf = ca.perf_snapshot()
+        results[mode] = (
+            float(np.asarray(net.blob("loss")).ravel()[0]),
+            np.asarray(net.blob("in0", diff=True)).copy(),
+            [np.asarray(net.param(i, diff=True)).copy()
+             for i in range(net.num_params())])
+    relu = perf.get("relu", {}).get("launches", 0)
+    eltwise = perf.get("eltwise", {}).get("launches", 0)
+    print(f"{name}: relu launches {relu}, eltwise launches {eltwise}")
+    assert relu == fg.relu_launches(expected)
+    assert eltwise == PARENT_ELTWISE_LAUNCHES[name]
+    lc, dc, pc = results["cpu"]
+    lg, dg, pg = results["gpu"]
+    tol = 1e-3
+    assert abs(lg - lc) < tol * max(1.0, abs(lc)), (lc, lg)
+    assert np.abs(dg - dc).max() < tol * max(np.abs(dc).max(), 1e-3)
+    for i, (a, b) in enumerate(zip(pc, pg)):
+        assert np.abs(b - a).max() < tol * max(np.abs(a).max(), 1e-3), \
+            f"param {i}"
+
+
+def test_eltwise_prod_is_an_error_in_gpu_mode():
+    # PROD runs in CPU mode only; with no GPU kernel for it, building the
+    # net in GPU mode fails by name instead of computing it somewhere else
+    import fusion_graphs as fg
+    ca.set_mode("gpu")
+    try:
+        net_from_text(fg.NEGATIVE["prod"][1])
+        raise AssertionError("expected Eltwise PROD to be refused")
+    except ca.CaffeError as e:
+        assert "PROD has no GPU kernel" in str(e), str(e)
+        assert "[in layer 'e1' (Eltwise) SetUp]" in str(e), str(e)
+    finally:
+        ca.set_mode("cpu")

@@ -209,6 +209,20 @@ def test_grad_eltwise_sum():
     check_gradients(net, "out", perturb_inputs=("in0", "in1"))
 
 
+def test_grad_eltwise_prod():
+    # three bottoms: each gradient is dy times the product of the other two
+    shapes = [(2, 3, 4, 4)] * 3
+    net = build_net("""layer { name: "e" type: "Eltwise" bottom: "in0"
+  bottom: "in1" bottom: "in2" top: "out"
+  eltwise_param { operation: PROD } }""", shapes)
+    for i in range(3):
+        net.set_blob(f"in{i}", seeded(shapes[i], seed=5 + i))
+    out = np.asarray(net.blob("in0")) * net.blob("in1") * net.blob("in2")
+    net.forward()
+    assert np.allclose(net.blob("out"), out, rtol=1e-6, atol=0)
+    check_gradients(net, "out", perturb_inputs=("in0", "in1", "in2"))
+
+
 def test_grad_relu():
     # direct bottom with kink exclusion, the reference's ReLU recipe
     # (GradientChecker kink=0, kink_range — skip elements near the kink)

@@ -103,6 +103,26 @@ def test_error_names_the_layer():
         raise AssertionError("expected a shape failure")
     except ca.CaffeError as e:
         assert "badconv" in str(e), str(e)
+    # the breadcrumb ends with the layer's scope, also when the layer threw:
+    # a failure outside every layer scope (wiring an unknown bottom, before
+    # SetUp; the net's first layer, so no layer scope opens before it) names
+    # its blob and carries no breadcrumb of the earlier layer
+    try:
+        net_from_text("""name: "t"
+layer { name: "lost" type: "ReLU" bottom: "nowhere" top: "out" }""")
+        raise AssertionError("expected an unknown-bottom failure")
+    except ca.CaffeError as e:
+        assert "unknown bottom blob nowhere" in str(e), str(e)
+        assert "[in " not in str(e), str(e)
+    # and a third failure, inside a layer again, carries its own layer's
+    body = """layer { name: "worseconv" type: "Convolution" bottom: "in0"
+  top: "out" convolution_param { num_output: 4 kernel_size: 9 } }"""
+    try:
+        net_from_text(input_net([(1, 3, 5, 5)], body))
+        raise AssertionError("expected a shape failure")
+    except ca.CaffeError as e:
+        assert "[in layer 'worseconv' (Convolution) SetUp]" in str(e), str(e)
+        assert "badconv" not in str(e), str(e)
 
 
 def test_unimplemented_options_fail_loudly():
