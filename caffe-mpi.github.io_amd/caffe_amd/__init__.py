@@ -88,6 +88,7 @@ _lib.caffe_set_compute.argtypes = [ctypes.c_char_p]
 _lib.caffe_gemm_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_kernel_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_net_fusions.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
+_lib.caffe_net_diff_sharing.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_fastdiv_selftest.argtypes = [ctypes.c_uint, ctypes.c_uint]
 _lib.caffe_fastdiv_selftest.restype = ctypes.c_long
 
@@ -320,13 +321,26 @@ class Net:
         (kind, producer layer, [absorbed layers]) per fusion, kind being
         bn_relu | conv_relu | sum_relu | bn_add | bn_add_relu (see
         caffe_amd.h).  The same in CPU mode, where nothing is fused."""
-        n = _lib.caffe_net_fusions(self._h, None, 0)
-        buf = ctypes.create_string_buffer(max(n, 0) + 1)
-        if n < 0 or _lib.caffe_net_fusions(self._h, buf, n + 1) < 0:
-            raise CaffeError(_lib.caffe_last_error().decode())
         return [(kind, prod, absorbed.split(","))
                 for kind, prod, absorbed in
-                (line.split(" ") for line in buf.value.decode().splitlines())]
+                self._plan_lines(_lib.caffe_net_fusions)]
+
+    def diff_sharing(self):
+        """Which bottoms share their layer's top gradient memory in GPU
+        mode, planned at build time, in layer order: one (layer, bottom
+        blob, "alias" | "copy") per propagating bottom of a unit Eltwise SUM
+        and of a one-top Split (see caffe_amd.h).  The same in CPU mode,
+        where every such bottom is copied."""
+        return [tuple(f) for f in
+                self._plan_lines(_lib.caffe_net_diff_sharing)]
+
+    def _plan_lines(self, read):
+        # a build-time plan: one entry per line, fields split by blanks
+        n = read(self._h, None, 0)
+        buf = ctypes.create_string_buffer(max(n, 0) + 1)
+        if n < 0 or read(self._h, buf, n + 1) < 0:
+            raise CaffeError(_lib.caffe_last_error().decode())
+        return [line.split(" ") for line in buf.value.decode().splitlines()]
 
     def blob(self, name, diff=False):
         shape = self.blob_shape(name)

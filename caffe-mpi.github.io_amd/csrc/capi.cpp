@@ -596,25 +596,46 @@ int caffe_kernel_trace_read(char* buf, int cap) {
   API_CATCH
 }
 
+// a build-time plan as text, one entry per line: whole lines only, like the
+// trace readers; returns the full length
+static int plan_lines(const std::vector<std::string>& lines, char* buf,
+                      int cap) {
+  std::string text;
+  if (cap > 0) buf[0] = 0;
+  for (auto& line : lines) {
+    if ((long)(text.size() + line.size() + 1) < (long)cap)
+      memcpy(buf + text.size(), (line + "\n").c_str(), line.size() + 2);
+    text += line + "\n";
+  }
+  return (int)text.size();
+}
+
 int caffe_net_fusions(caffe_net_t n, char* buf, int cap) {
   API_TRY
   static const char* const kinds[] = {"bn_relu", "conv_relu", "sum_relu",
                                       "bn_add", "bn_add_relu"};
   auto& layers = N(n)->layers();
-  std::string text;
-  if (cap > 0) buf[0] = 0;
+  std::vector<std::string> lines;
   for (auto& f : N(n)->fusions()) {
     std::string line = std::string(kinds[f.kind]) + " " +
                        layers[f.producer]->name();
     for (size_t k = 0; k < f.absorbed.size(); ++k)
       line += (k ? "," : " ") + layers[f.absorbed[k]]->name();
-    line += "\n";
-    // whole lines only, like the trace readers
-    if ((long)(text.size() + line.size()) < (long)cap)
-      memcpy(buf + text.size(), line.c_str(), line.size() + 1);
-    text += line;
+    lines.push_back(line);
   }
-  return (int)text.size();
+  return plan_lines(lines, buf, cap);
+  API_CATCH
+}
+
+int caffe_net_diff_sharing(caffe_net_t n, char* buf, int cap) {
+  API_TRY
+  auto& layers = N(n)->layers();
+  std::vector<std::string> lines;
+  for (auto& s : N(n)->diff_sharing())
+    lines.push_back(layers[s.layer]->name() + " " +
+                    layers[s.layer]->param()->strs("bottom")[s.bottom] +
+                    (s.alias ? " alias" : " copy"));
+  return plan_lines(lines, buf, cap);
   API_CATCH
 }
 

@@ -292,8 +292,9 @@ class BatchNormLayer : public Layer {
   bool fuse_relu_ = false;  // GPU graph fusion: BN+ReLU forward in one pass
   // GPU graph fusion: a following Eltwise(SUM) absorbed into the norm
   // epilogue — forward writes fuse_add_out_ = bn(x) + fuse_add_other_
-  // (bit-identical to the separate add; backward is untouched, the
-  // eltwise aliases the sum's diff onto this layer's top)
+  // (bit-identical to the separate add; backward is untouched: this
+  // layer's top reads the sum's gradient as Net::plan_diff_sharing
+  // arranged it for the eltwise, shared memory or a copy)
   Blob* fuse_add_other_ = nullptr;
   Blob* fuse_add_out_ = nullptr;
   bool fuse_add_relu_ = false;
@@ -415,8 +416,8 @@ class EltwiseLayer : public Layer {
                     const std::vector<Blob*>&) override;
   std::vector<float> coeffs_;
   std::string op_ = "SUM";
-  // a plain sum: what the add3 forward, the diff-aliasing backward and
-  // the graph fusions require
+  // a plain sum: what the add3 forward, the diff sharing of the backward
+  // and the graph fusions require
   bool unit_sum() const {
     bool ones = op_ == "SUM";
     for (float c : coeffs_) ones = ones && c == 1.f;
@@ -424,6 +425,10 @@ class EltwiseLayer : public Layer {
   }
   bool fuse_relu_ = false;  // GPU graph fusion: SUM+ReLU forward in one pass
   bool fused_away_ = false;  // producing BN writes bn(x)+other directly
+  // GPU, unit sum: bottom i's diff shares the top's diff memory, so
+  // backward launches nothing for it (set from Net::plan_diff_sharing; a
+  // bottom without it gets a copy)
+  std::vector<bool> alias_diff_;
 };
 
 class LRNLayer : public Layer {
@@ -502,6 +507,9 @@ class SplitLayer : public Layer {
                     const std::vector<Blob*>&) override;
   void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
                     const std::vector<Blob*>&) override;
+  // GPU, one top: the bottom's diff shares the top's diff memory and
+  // backward launches nothing (set from Net::plan_diff_sharing)
+  bool alias_diff_ = false;
 };
 
 class SoftmaxLayer : public Layer {

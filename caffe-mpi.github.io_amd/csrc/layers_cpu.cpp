@@ -761,6 +761,7 @@ void EltwiseLayer::LayerSetUp(const std::vector<Blob*>& bottom,
       << "only Eltwise SUM is on the hot path: " << op_
       << " has no GPU kernel";
   coeffs_.assign(bottom.size(), 1.f);
+  alias_diff_.assign(bottom.size(), false);
   if (ep) {
     auto cs = ep->nums("coeff");
     // reference eltwise_layer.cpp LayerSetUp
@@ -1013,14 +1014,10 @@ void SplitLayer::Backward_cpu(const std::vector<Blob*>& top,
 void SplitLayer::Backward_gpu(const std::vector<Blob*>& top,
                               const std::vector<bool>& prop_down,
                               const std::vector<Blob*>& bottom) {
-  if (!prop_down[0]) return;
+  if (!prop_down[0] || alias_diff_) return;
   Engine& E = Engine::get();
   const long n = bottom[0]->count();
   float* dx = bottom[0]->mutable_gpu_diff();
-  if (top.size() == 1) {
-    bottom[0]->ShareDiff(*top[0]);
-    return;
-  }
   if (top.size() == 2) {  // single fused pass for the common fan-out of 2
     gpu::add3(E.stream, n, top[0]->gpu_diff(), top[1]->gpu_diff(), dx);
     return;

@@ -495,20 +495,19 @@ void EltwiseLayer::Backward_gpu(const std::vector<Blob*>& top,
                                 const std::vector<Blob*>& bottom) {
   Engine& E = Engine::get();
   const long n = top[0]->count();
-  if (unit_sum()) {
-    // dx_i == dy exactly: alias the diffs instead of copying (zero kernels;
-    // safe because each bottom's diff is consumed before anything rewrites
-    // the shared buffer — backward runs top-down on one stream)
-    for (size_t i = 0; i < bottom.size(); ++i)
-      if (prop_down[i]) bottom[i]->ShareDiff(*top[0]);
-    return;
-  }
   CHECK_(op_ == "SUM") << "Eltwise " << op_ << " has no GPU kernel";
-  const float* dy = top[0]->gpu_diff();
+  const bool unit = unit_sum();
   for (size_t i = 0; i < bottom.size(); ++i) {
-    if (!prop_down[i]) continue;
+    // dx_i == dy exactly in a unit sum: nothing to launch for a bottom that
+    // shares dy's memory (Net::plan_diff_sharing), a copy for one that
+    // keeps its own
+    if (!prop_down[i] || (unit && alias_diff_[i])) continue;
+    const float* dy = top[0]->gpu_diff();
     float* dx = bottom[i]->mutable_gpu_diff();
-    gpu::axpby(E.stream, n, coeffs_[i], dy, 0.f, dx);
+    if (unit)
+      gpu::copy(E.stream, n, dy, dx);
+    else
+      gpu::axpby(E.stream, n, coeffs_[i], dy, 0.f, dx);
   }
 }
 

@@ -135,8 +135,10 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
   set_backward_flags(msg->boolean("force_backward", false));
   collect_params();
   fusions_ = plan_fusions();
+  diff_sharing_ = plan_diff_sharing();
   if (Engine::get().mode == Mode::GPU) {
     apply_fusions();
+    apply_diff_sharing();
     setup_arena();
   }
 }
@@ -374,6 +376,73 @@ void Net::apply_fusions() {
         static_cast<EltwiseLayer*>(layers_[a].get())->fused_away_ = true;
       }
     }
+  }
+}
+
+// ------------------------------------------------------ diff-sharing plan
+bool Net::passes_diff_through(int i) const {
+  if (auto* el = dynamic_cast<EltwiseLayer*>(layers_[i].get()))
+    return el->unit_sum();
+  return dynamic_cast<SplitLayer*>(layers_[i].get()) && tops_[i].size() == 1;
+}
+
+int Net::producer(const Blob* blob) const {
+  for (int i = 0; i < (int)layers_.size(); ++i)
+    for (auto* t : tops_[i])
+      if (t == blob) return i;
+  return -1;
+}
+
+int Net::last_diff_writer(int i, const Blob* blob) const {
+  for (int k = i - 1; k >= 0; --k) {
+    if (!in_place(k) || tops_[k][0] != blob) continue;
+    // every in-place backward writes the diff but that of a ReLU a BN
+    // absorbed in both directions, which launches nothing
+    bool absorbed = false;
+    for (auto& f : fusions_)
+      absorbed = absorbed || (f.kind == Fusion::BN_RELU && f.absorbed[0] == k);
+    if (!absorbed) return k;
+  }
+  return -1;
+}
+
+// Backward runs from the last layer to the first on one stream.  A bottom
+// that shares the top's diff memory is read last by its producer; an
+// in-place layer on it writes that memory before.  If the write comes
+// while another bottom of the same layer still waits to be read (its
+// producer is not above the writer), that bottom would read the written
+// gradient: this one keeps its own memory.  The top of a Flatten already
+// shares its diff with the Flatten's bottom and is never re-pointed.
+bool Net::may_alias_diff(int i, int b) const {
+  const Blob* blob = bottoms_[i][b];
+  if (dynamic_cast<FlattenLayer*>(layers_[producer(blob)].get())) return false;
+  const int writer = last_diff_writer(i, blob);
+  for (int j = 0; j < (int)bottoms_[i].size() && writer >= 0; ++j)
+    if (j != b && prop_down_[i][j] && producer(bottoms_[i][j]) <= writer)
+      return false;
+  return true;
+}
+
+std::vector<Net::DiffShare> Net::plan_diff_sharing() const {
+  std::vector<DiffShare> plan;
+  for (int i = 0; i < (int)layers_.size(); ++i)
+    for (int b = 0; passes_diff_through(i) && b < (int)bottoms_[i].size(); ++b)
+      if (prop_down_[i][b]) plan.push_back({i, b, may_alias_diff(i, b)});
+  return plan;
+}
+
+// Share the diffs once, last layer first as backward would meet them: a top
+// that is itself an aliased bottom of a later layer is re-pointed before
+// its own bottoms take its memory.  No blob is reshaped after the build.
+void Net::apply_diff_sharing() {
+  for (auto s = diff_sharing_.rbegin(); s != diff_sharing_.rend(); ++s) {
+    if (!s->alias) continue;
+    bottoms_[s->layer][s->bottom]->ShareDiff(*tops_[s->layer][0]);
+    Layer* l = layers_[s->layer].get();
+    if (auto* el = dynamic_cast<EltwiseLayer*>(l))
+      el->alias_diff_[s->bottom] = true;
+    else
+      static_cast<SplitLayer*>(l)->alias_diff_ = true;
   }
 }
 

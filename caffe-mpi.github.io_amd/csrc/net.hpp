@@ -138,6 +138,18 @@ class Net {
   // in layer order of the producers
   const std::vector<Fusion>& fusions() const { return fusions_; }
 
+  // A bottom whose gradient equals its layer's top gradient (a unit Eltwise
+  // SUM, a Split with one top) either shares the top's diff memory, so the
+  // layer's backward launches nothing for it, or keeps its own and gets a
+  // copy.  Planned from the built graph in both modes like the fusions;
+  // only GPU mode applies it (the CPU layers always copy).
+  struct DiffShare {
+    int layer, bottom;  // layer index, index among its bottoms
+    bool alias;
+  };
+  // in layer order, then bottom order
+  const std::vector<DiffShare>& diff_sharing() const { return diff_sharing_; }
+
  private:
   // the net build, in order; each step reads and writes the members below
   void init(const PMsgPtr& msg, int batch_override);
@@ -148,16 +160,29 @@ class Net {
   void collect_params();
   std::vector<Fusion> plan_fusions() const;
   void apply_fusions();
+  std::vector<DiffShare> plan_diff_sharing() const;
+  void apply_diff_sharing();
   void setup_arena();
 
-  // the graph predicates the fusion plan is made of
-  bool in_place(int i) const { return bottoms_[i][0] == tops_[i][0]; }
+  // the graph predicates the two plans are made of
+  bool in_place(int i) const {
+    return !bottoms_[i].empty() && !tops_[i].empty() &&
+           bottoms_[i][0] == tops_[i][0];
+  }
   bool slope0_relu(int i) const;  // one-bottom one-top ReLU, slope 0
   bool unit_sum2(int i) const;    // Eltwise SUM of two bottoms, coeffs 1
   // layer i-1 has one top and that top is `blob`
   bool fed_by_previous(int i, const Blob* blob) const {
     return i >= 1 && tops_[i - 1].size() == 1 && tops_[i - 1][0] == blob;
   }
+  // every bottom's gradient is the top's: unit Eltwise SUM, one-top Split
+  bool passes_diff_through(int i) const;
+  int producer(const Blob* blob) const;  // the first layer with this top
+  // the last layer below `i` whose backward writes `blob`'s diff in place,
+  // or -1
+  int last_diff_writer(int i, const Blob* blob) const;
+  // bottom `b` of layer `i` may share the top's diff memory
+  bool may_alias_diff(int i, int b) const;
 
   // one layer's dispatch under its error scope
   void forward_layer(size_t i);
@@ -174,6 +199,7 @@ class Net {
   std::map<std::string, std::shared_ptr<Blob>> blob_map_;
   std::vector<LParam> params_;
   std::vector<Fusion> fusions_;
+  std::vector<DiffShare> diff_sharing_;
   long arena_count_ = 0;
   float* diff_arena_ = nullptr;
   std::vector<hipEvent_t> layer_events_;

@@ -218,6 +218,17 @@ int caffe_kernel_trace_read(char* buf, int cap);
  * depends on the graph alone and is the same in CPU mode, where nothing
  * is fused. */
 int caffe_net_fusions(caffe_net_t net, char* buf, int cap);
+/* Which bottoms share their layer's top gradient memory, planned at build
+ * time like the fusions and read the same way: one line "layer bottom
+ * alias|copy" (a layer name, then the name of one of its bottom blobs) per
+ * propagating bottom of an Eltwise SUM with every coefficient 1 and of a
+ * Split with one top, in layer order, then bottom order.  alias: the GPU
+ * backward launches nothing for that bottom; copy: a layer in place on the
+ * bottom would write the shared memory while another bottom's gradient is
+ * still unread, or the bottom is a Flatten's top, so it keeps its own memory
+ * and gets one copy.  The same in CPU mode, where every such bottom is
+ * copied. */
+int caffe_net_diff_sharing(caffe_net_t net, char* buf, int cap);
 /* Self-test of the exact fast division the GEMM staging decomposes its view
  * indices with (host code, no GPU): for every divisor in [d_lo, d_hi]
  * compares quotient and remainder with / and % over the dividends 0..2^20,

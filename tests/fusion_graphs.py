@@ -1,11 +1,13 @@
-"""Hand-written graphs for the graph-fusion plan (Net.fusions()), shared by
-tests/test_fusion_plan.py (the plan, without a GPU) and
-tests/test_gpu_graph_fuzz.py (what the GPU launches for it).
+"""Hand-written graphs for the two build-time plans of a net, the graph
+fusions (Net.fusions()) and the gradient-buffer sharing (Net.diff_sharing()),
+shared by tests/test_fusion_plan.py and tests/test_diff_sharing_plan.py (the
+plans, without a GPU) and tests/test_gpu_graph_fuzz.py (what the GPU
+launches for them).
 
 Every graph reads an Input of 2x4x8x8 (in0) with labels (in1), is closed by
 InnerProduct + SoftmaxWithLoss and holds exactly one ReLU.  Layer names:
 c1 conv, b1 BatchNorm, s1 / s2 shortcut 1x1 convs, e1 the sum, r1 the ReLU,
-e2 / x1 extra consumers.
+e2 / x1 extra consumers, f1 / f2 Flatten, sp an explicit Split.
 """
 
 SHAPE = (2, 4, 8, 8)
@@ -34,6 +36,16 @@ def elt(name, bottoms, top, param="operation: SUM"):
     bs = " ".join(f'bottom: "{b}"' for b in bottoms)
     return (f'layer {{ name: "{name}" type: "Eltwise" {bs} top: "{top}" '
             f'eltwise_param {{ {param} }} }}')
+
+
+def flatten(name, bottom, top):
+    return (f'layer {{ name: "{name}" type: "Flatten" bottom: "{bottom}" '
+            f'top: "{top}" }}')
+
+
+def split(name, bottom, top):
+    return (f'layer {{ name: "{name}" type: "Split" bottom: "{bottom}" '
+            f'top: "{top}" }}')
 
 
 def net(layers, out):
@@ -133,6 +145,91 @@ UNFUSED_TWIN = {
 UNFUSED_TWIN["residual_bn_second"] = UNFUSED_TWIN["residual"].replace(
     'bottom: "b" bottom: "s"', 'bottom: "s" bottom: "b"')
 UNFUSED_TWIN["residual_relu_out"] = UNFUSED_TWIN["residual"]
+
+
+# Graphs for the diff-sharing plan: an in-place layer, a Flatten or a
+# one-top Split next to a unit sum.  name -> (prototxt, phase, expected
+# Net.fusions())
+SHARING = {
+    # in_place_bn with the shortcut conv after the in-place BN
+    "in_place_bn_shortcut_second": (
+        net([conv("c1", "in0", "a"), bn("b1", "a", "a"),
+             conv("s1", "in0", "s", k=1), elt("e1", ("a", "s"), "e"),
+             relu("r1", "e", "e")], "e"), 0, [("sum_relu", "e1", ["r1"])]),
+    "in_place_relu_bottom": (
+        net([conv("s1", "in0", "s", k=1), conv("c1", "in0", "a"),
+             relu("r1", "a", "a"), elt("e1", ("a", "s"), "e")], "e"), 0,
+        [("conv_relu", "c1", ["r1"])]),
+    "bn_relu_bottom": (
+        net([conv("s1", "in0", "s", k=1), conv("c1", "in0", "a"),
+             bn("b1", "a", "b"), relu("r1", "b", "b"),
+             elt("e1", ("b", "s"), "e")], "e"), 0,
+        [("bn_relu", "b1", ["r1"])]),
+    "three_bottoms_in_place": (
+        net([conv("s1", "in0", "s", k=1), conv("s2", "in0", "t", k=1),
+             conv("c1", "in0", "a"), bn("b1", "a", "a"),
+             elt("e1", ("a", "s", "t"), "e"), relu("r1", "e", "e")], "e"),
+        0, []),
+    "flatten_into_sum": (
+        net([conv("s1", "in0", "s", k=1), conv("c1", "in0", "a"),
+             flatten("f1", "a", "fa"), flatten("f2", "s", "fs"),
+             elt("e1", ("fa", "fs"), "e"), relu("r1", "e", "e")], "e"), 0,
+        [("sum_relu", "e1", ["r1"])]),
+    "single_top_split": (
+        net([conv("c1", "in0", "a"), split("sp", "a", "a1"),
+             relu("r1", "a1", "f")], "f"), 0, []),
+    "single_top_split_after_flatten": (
+        net([conv("c1", "in0", "a"), flatten("f1", "a", "fa"),
+             split("sp", "fa", "fb"), relu("r1", "fb", "f")], "f"), 0, []),
+}
+
+
+def _alias(layer, *bottoms):
+    return [(layer, b, "alias") for b in bottoms]
+
+
+# name -> expected Net.diff_sharing(), for every graph above.  Written from
+# the rule ("Gradient-buffer sharing"): an entry per propagating
+# bottom of a unit sum or a one-top Split; "copy" where a layer in place on
+# the bottom writes its gradient at or above the producer of another bottom
+# of the same layer (a ReLU absorbed by a bn_relu fusion writes nothing),
+# and for the top of a Flatten; "alias" otherwise.
+DIFF_SHARING = {
+    "bn_relu": [], "conv_relu": [], "leaky_relu": [],
+    "bn_relu_out_of_place": [], "coeff_half": [], "prod": [],
+    "residual": _alias("e1", "b", "s"),
+    "residual_bn_second": _alias("e1", "s", "b"),
+    "residual_relu_out": _alias("e1", "b", "s"),
+    "test_phase": _alias("e1", "b", "s"),
+    "conv_between": _alias("e1", "b", "s"),
+    "three_bottoms": _alias("e1", "b", "s", "t"),
+    # the Split of e behind e1 has two tops and is not in the plan
+    "sum_twice": _alias("e1", "b", "s") + _alias("e2", "f", "e_split_1"),
+    # b1 (in place on a) runs its backward before s1, which reads s
+    "in_place_bn": [("e1", "a", "copy"), ("e1", "s", "alias")],
+    # r1 is in place on e, only its forward is fused, and it sits above
+    # the Split that produces b_split_1
+    "bn_out_twice": (_alias("e1", "b_split_0", "s") +
+                     [("e2", "e", "copy"), ("e2", "b_split_1", "alias")]),
+    # the shortcut conv after the BN: s1 has read s by the time b1 writes
+    "in_place_bn_shortcut_second": _alias("e1", "a", "s"),
+    "in_place_relu_bottom": [("e1", "a", "copy"), ("e1", "s", "alias")],
+    # b1 absorbed r1's backward: nothing writes b's gradient in place
+    "bn_relu_bottom": _alias("e1", "b", "s"),
+    "three_bottoms_in_place": ([("e1", "a", "copy")] +
+                               _alias("e1", "s", "t")),
+    "flatten_into_sum": [("e1", "fa", "copy"), ("e1", "fs", "copy")],
+    "single_top_split": _alias("sp", "a"),
+    "single_top_split_after_flatten": [("sp", "fa", "copy")],
+}
+
+
+def all_graphs():
+    """name -> (prototxt, phase, expected Net.fusions()) of every graph"""
+    out = dict(POSITIVE)
+    out.update({n: v[1:] for n, v in NEGATIVE.items()})
+    out.update(SHARING)
+    return out
 
 
 def relu_launches(fusions):

@@ -172,32 +172,39 @@ def test_gpu_graph_fusion_parity(seed, dtype):
 
 
 # eltwise-class launches (add3, axpby, copy, ... of one forward + backward)
-# of the hand graphs as measured on the parent commit b1ffb37 on the MI355X:
-# the fusion flags moved from two passes in Net::init to a plan, and what
-# the GPU launches for a graph must not have moved with them
+# of the hand graphs as measured on a parent commit on the MI355X: the first
+# eight on b1ffb37, when the fusion flags moved from two passes in Net::init
+# to a plan, the others on 69f1c0a, when the diff sharing moved from the
+# Eltwise and Split backward to a plan.  What the GPU launches for a graph
+# must not move with either, but for one copy per "copy" entry of the diff
+# sharing plan, where the parent shared memory that was still to be read.
 PARENT_ELTWISE_LAUNCHES = {
     "bn_relu": 0, "conv_relu": 0, "residual": 1, "residual_bn_second": 1,
     "residual_relu_out": 1, "leaky_relu": 0, "conv_between": 2,
     "sum_twice": 3,
+    "bn_relu_out_of_place": 0, "bn_out_twice": 4, "coeff_half": 5,
+    "three_bottoms": 6, "in_place_bn": 3, "test_phase": 2,
+    "in_place_bn_shortcut_second": 3, "in_place_relu_bottom": 2,
+    "bn_relu_bottom": 2, "three_bottoms_in_place": 7, "flatten_into_sum": 2,
+    "single_top_split": 0, "single_top_split_after_flatten": 0,
 }
 
+# every hand graph but `prod`, which builds in CPU mode only
+HAND_GRAPHS = [
+    "bn_relu", "conv_relu", "residual", "residual_bn_second",
+    "residual_relu_out", "leaky_relu", "bn_relu_out_of_place",
+    "conv_between", "bn_out_twice", "sum_twice", "coeff_half",
+    "three_bottoms", "in_place_bn", "test_phase",
+    "in_place_bn_shortcut_second", "in_place_relu_bottom", "bn_relu_bottom",
+    "three_bottoms_in_place", "flatten_into_sum", "single_top_split",
+    "single_top_split_after_flatten",
+]
 
-def _hand_graphs():
+
+@pytest.mark.parametrize("name", HAND_GRAPHS)
+def test_hand_graph_launches_and_parity(name):
     import fusion_graphs as fg
-    # every positive graph, each followed by its nearest negative: the first
-    # one that was derived from it
-    out = []
-    for name, g in fg.POSITIVE.items():
-        out.append((name,) + g)
-        near = [(n,) + v[1:] for n, v in fg.NEGATIVE.items() if v[0] == name]
-        out += near[:1]
-    return out
-
-
-@pytest.mark.parametrize("name,text,phase,expected",
-                         _hand_graphs(), ids=[g[0] for g in _hand_graphs()])
-def test_hand_graph_launches_and_parity(name, text, phase, expected):
-    import fusion_graphs as fg
+    text, phase, expected = fg.all_graphs()[name]
     rng = np.random.default_rng(11)
     x = rng.standard_normal(fg.SHAPE).astype(np.float32)
     labels = rng.integers(0, 4, fg.SHAPE[0]).astype(np.float32)
@@ -207,6 +214,7 @@ def test_hand_graph_launches_and_parity(name, text, phase, expected):
         ca.set_random_seed(2024)
         net = net_from_text(text, phase=phase)
         assert net.fusions() == expected
+        assert net.diff_sharing() == fg.DIFF_SHARING[name]
         net.set_blob("in0", x)
         net.set_blob("in1", labels)
         ca.device_synchronize()
@@ -222,9 +230,11 @@ def test_hand_graph_launches_and_parity(name, text, phase, expected):
              for i in range(net.num_params())])
     relu = perf.get("relu", {}).get("launches", 0)
     eltwise = perf.get("eltwise", {}).get("launches", 0)
-    print(f"{name}: relu launches {relu}, eltwise launches {eltwise}")
+    copies = [d for _, _, d in fg.DIFF_SHARING[name]].count("copy")
+    print(f"{name}: relu launches {relu}, eltwise launches {eltwise}, "
+          f"{copies} of them planned copies")
     assert relu == fg.relu_launches(expected)
-    assert eltwise == PARENT_ELTWISE_LAUNCHES[name]
+    assert eltwise == PARENT_ELTWISE_LAUNCHES[name] + copies
     lc, dc, pc = results["cpu"]
     lg, dg, pg = results["gpu"]
     tol = 1e-3
