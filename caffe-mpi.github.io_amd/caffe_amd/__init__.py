@@ -89,6 +89,7 @@ _lib.caffe_gemm_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_kernel_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_net_fusions.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_net_diff_sharing.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
+_lib.caffe_net_param_sharing.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_fastdiv_selftest.argtypes = [ctypes.c_uint, ctypes.c_uint]
 _lib.caffe_fastdiv_selftest.restype = ctypes.c_long
 
@@ -257,7 +258,10 @@ def kernel_trace_read():
     C, blocks (softmax); lo, hi, nseg (update bucket range in the param
     arena: sgd_seg for SGD with L2, solver_seg for every other solver type
     and for L1, which adds rule (sgd | nesterov | adagrad | rmsprop |
-    adadelta | adam) and reg (L1 | L2))."""
+    adadelta | adam) and reg (L1 | L2)); shared_diff_sum (the sum of shared
+    params' gradients after an owner layer's backward) with lo, hi, nseg,
+    nsrc; contrastive_fwd | contrastive_bwd with var (row_thread | row_wave),
+    N, C, blocks."""
     return _trace_records(_lib.caffe_kernel_trace_read)
 
 
@@ -333,6 +337,17 @@ class Net:
         where every such bottom is copied."""
         return [tuple(f) for f in
                 self._plan_lines(_lib.caffe_net_diff_sharing)]
+
+    def param_sharing(self):
+        """The shared params planned at build time, in layer order: one
+        (layer, blob index, param name, owner layer, owner blob index) per
+        param blob that shares an earlier blob of the same ParamSpec name
+        (see caffe_amd.h).  A sharer uses the owner's weights and is not
+        among num_params() / param(); its gradient is added into the
+        owner's during backward.  The same in CPU mode."""
+        return [(layer, int(bi), name, owner, int(obi))
+                for layer, bi, name, owner, obi in
+                self._plan_lines(_lib.caffe_net_param_sharing)]
 
     def _plan_lines(self, read):
         # a build-time plan: one entry per line, fields split by blanks

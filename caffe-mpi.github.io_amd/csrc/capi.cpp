@@ -639,6 +639,18 @@ int caffe_net_diff_sharing(caffe_net_t n, char* buf, int cap) {
   API_CATCH
 }
 
+int caffe_net_param_sharing(caffe_net_t n, char* buf, int cap) {
+  API_TRY
+  auto& layers = N(n)->layers();
+  std::vector<std::string> lines;
+  for (auto& s : N(n)->param_sharing())
+    lines.push_back(layers[s.layer]->name() + " " + std::to_string(s.blob) +
+                    " " + s.name + " " + layers[s.owner_layer]->name() + " " +
+                    std::to_string(s.owner_blob));
+  return plan_lines(lines, buf, cap);
+  API_CATCH
+}
+
 int caffe_perf_reset(void) {
   for (auto& kv : Engine::get().perf()) {
     kv.second.launches = 0;

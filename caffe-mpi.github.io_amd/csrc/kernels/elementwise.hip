@@ -38,10 +38,10 @@ enum KOp {
   kPoolMaxFwd, kPoolMaxBwd, kPoolAveFwd, kPoolAveBwd, kBnFwdStats,
   kBnBwdStats, kLrnFwd, kLrnBwd, kSoftmaxFwd, kSgdSeg, kSolverSeg,
   kSigmoidFwd, kSigmoidBwd, kSigmoidCeFwd, kSigmoidCeBwd, kEuclidFwd,
-  kEuclidBwd
+  kEuclidBwd, kSharedDiffSum, kContrastiveFwd, kContrastiveBwd
 };
 enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
-            kVarScalar, kVarRing5 };
+            kVarScalar, kVarRing5, kVarRowThread, kVarRowWave };
 struct KernelRec {
   long a, b, c, d;  // per-op fields, see kernel_trace_read
   unsigned char op, var;
@@ -78,12 +78,15 @@ long kernel_trace_read(char* buf, long cap) {
       "bn_fwd_stats", "bn_bwd_stats", "lrn_fwd",      "lrn_bwd",
       "softmax_fwd",  "sgd_seg",      "solver_seg",   "sigmoid_fwd",
       "sigmoid_bwd",  "sigmoid_ce_fwd", "sigmoid_ce_bwd", "euclid_fwd",
-      "euclid_bwd"};
+      "euclid_bwd",   "shared_diff_sum", "contrastive_fwd",
+      "contrastive_bwd"};
   // solver_seg keeps rule * 2 + l1 in the var byte
   static const char* const rule[] = {"sgd",     "nesterov", "adagrad",
                                      "rmsprop", "adadelta", "adam"};
-  static const char* const var[] = {"",        "k3", "k3s1",   "k3s2",
-                                    "generic", "v4", "scalar", "ring5"};
+  static const char* const var[] = {"",        "k3",     "k3s1",
+                                    "k3s2",    "generic", "v4",
+                                    "scalar",  "ring5",  "row_thread",
+                                    "row_wave"};
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   long len = 0;
   if (cap > 0) buf[0] = 0;
@@ -132,6 +135,16 @@ long kernel_trace_read(char* buf, long cap) {
         n = snprintf(line, sizeof(line),
                      "op=%s n=%ld blocks=%ld partials=%ld passes=%ld\n",
                      op[r.op], r.a, r.b, r.c, r.d);
+        break;
+      case kSharedDiffSum:
+        n = snprintf(line, sizeof(line),
+                     "op=%s lo=%ld hi=%ld nseg=%ld nsrc=%ld\n", op[r.op], r.a,
+                     r.b, r.c, r.d);
+        break;
+      case kContrastiveFwd:
+      case kContrastiveBwd:
+        n = snprintf(line, sizeof(line), "op=%s var=%s N=%ld C=%ld blocks=%ld\n",
+                     op[r.op], var[r.var], r.a, r.b, r.c);
         break;
       default:
         n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld\n",
@@ -1619,6 +1632,152 @@ void euclid_bwd(hipStream_t s, const float* a, const float* b, long n,
   ktrace(kEuclidBwd, kVarNone, n, g.blocks, g.passes);
 }
 
+// ContrastiveLoss over a [N][C], b [N][C], sim [N].  Two row mappings: one
+// thread per row while a row is narrower than a wave (the siamese net has
+// C = 2; a wave per row would idle most lanes), one wave per row from
+// kContrastiveWaveC on (a thread per row would walk C elements with its
+// neighbours C floats apart, uncoalesced).  The switch point comes from
+// reading the two loops, not from a measurement.  Both index rows by scalar
+// element, so neither needs C % 4 == 0 or a 16-byte-aligned row start.
+// The forward stores each row's d² (double sum in a fixed order, rounded to
+// float once) for the backward and feeds the row's loss term into the
+// two-stage sum above: one double per thread, block_sum, k_loss_final.
+constexpr int kWave = 64;
+constexpr int kContrastiveWaveC = kWave;
+static inline bool contrastive_row_wave(int C) {
+  return C >= kContrastiveWaveC;
+}
+static inline int contrastive_blocks(int N, int C) {
+  const long rows_per_block = contrastive_row_wave(C) ? TPB / kWave : TPB;
+  return (int)std::min<long>(2048, std::max<long>(
+                                       1, (N + rows_per_block - 1) /
+                                              rows_per_block));
+}
+int contrastive_partials(int N, int C) { return contrastive_blocks(N, C); }
+
+// lane 0 of the wave returns the sum, added in a fixed tree
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+  return v;
+}
+
+template <bool kRowWave>
+__global__ void k_contrastive_fwd(const float* __restrict__ a,
+                                  const float* __restrict__ b,
+                                  const float* __restrict__ sim, int N, int C,
+                                  float margin, int legacy,
+                                  float* __restrict__ dist_sq,
+                                  double* __restrict__ partials) {
+  double acc = 0;
+  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const long nthreads = (long)gridDim.x * blockDim.x;
+  if (kRowWave) {
+    const int lane = threadIdx.x % kWave;
+    for (long r = tid / kWave; r < N; r += nthreads / kWave) {
+      const float* ar = a + r * C;
+      const float* br = b + r * C;
+      double s = 0;
+      for (int c = lane; c < C; c += kWave) {
+        const float d = ar[c] - br[c];
+        s += (double)d * (double)d;
+      }
+      s = wave_sum(s);
+      if (lane == 0) {
+        const float dsq = (float)s;
+        dist_sq[r] = dsq;
+        acc += (double)contrastive_row_loss(dsq, (int)sim[r] != 0, margin,
+                                            legacy != 0);
+      }
+    }
+  } else {
+    for (long r = tid; r < N; r += nthreads) {
+      const float* ar = a + r * C;
+      const float* br = b + r * C;
+      double s = 0;
+      for (int c = 0; c < C; ++c) {
+        const float d = ar[c] - br[c];
+        s += (double)d * (double)d;
+      }
+      const float dsq = (float)s;
+      dist_sq[r] = dsq;
+      acc += (double)contrastive_row_loss(dsq, (int)sim[r] != 0, margin,
+                                          legacy != 0);
+    }
+  }
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+
+void contrastive_fwd(hipStream_t s, const float* a, const float* b,
+                     const float* sim, int N, int C, float margin,
+                     bool legacy, float* dist_sq, double* partials,
+                     float* loss_out) {
+  PerfScope perf(PERF_CLASS("loss"), s, 0, 8.0 * N * C + 8.0 * N);
+  const int blocks = contrastive_blocks(N, C);
+  const bool wave = contrastive_row_wave(C);
+  if (wave)
+    hipLaunchKernelGGL(k_contrastive_fwd<true>, dim3(blocks), dim3(TPB), 0, s,
+                       a, b, sim, N, C, margin, legacy ? 1 : 0, dist_sq,
+                       partials);
+  else
+    hipLaunchKernelGGL(k_contrastive_fwd<false>, dim3(blocks), dim3(TPB), 0, s,
+                       a, b, sim, N, C, margin, legacy ? 1 : 0, dist_sq,
+                       partials);
+  hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(TPB), 0, s,
+                     (const double*)partials, blocks, 0.5 / N, loss_out);
+  ktrace(kContrastiveFwd, wave ? kVarRowWave : kVarRowThread, N, C, blocks);
+}
+
+// a - b is recomputed; the row's coefficient comes from its stored d².
+// da / db null = that bottom takes no gradient.  db's coefficient is da's
+// negated (alpha only changes sign), and a zero coefficient writes exact
+// zeros as the reference's caffe_set does.
+template <bool kRowWave>
+__global__ void k_contrastive_bwd(const float* __restrict__ a,
+                                  const float* __restrict__ b,
+                                  const float* __restrict__ sim,
+                                  const float* __restrict__ dist_sq, int N,
+                                  int C, float margin, int legacy, float alpha,
+                                  float* __restrict__ da,
+                                  float* __restrict__ db) {
+  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const long nthreads = (long)gridDim.x * blockDim.x;
+  const long r0 = kRowWave ? tid / kWave : tid;
+  const long rstep = kRowWave ? nthreads / kWave : nthreads;
+  const int c0 = kRowWave ? threadIdx.x % kWave : 0;
+  const int cstep = kRowWave ? kWave : 1;
+  for (long r = r0; r < N; r += rstep) {
+    const float coef = contrastive_row_beta(dist_sq[r], (int)sim[r] != 0,
+                                            margin, legacy != 0, alpha);
+    for (int c = c0; c < C; c += cstep) {
+      const long i = r * C + c;
+      const float g = coef == 0.f ? 0.f : coef * (a[i] - b[i]);
+      if (da) da[i] = g;
+      if (db) db[i] = -g;
+    }
+  }
+}
+
+void contrastive_bwd(hipStream_t s, const float* a, const float* b,
+                     const float* sim, const float* dist_sq, int N, int C,
+                     float margin, bool legacy, float alpha, float* da,
+                     float* db) {
+  PerfScope perf(PERF_CLASS("loss"), s, 0,
+                 (8.0 + (da ? 4.0 : 0.0) + (db ? 4.0 : 0.0)) * N * C);
+  const int blocks = contrastive_blocks(N, C);
+  const bool wave = contrastive_row_wave(C);
+  if (wave)
+    hipLaunchKernelGGL(k_contrastive_bwd<true>, dim3(blocks), dim3(TPB), 0, s,
+                       a, b, sim, dist_sq, N, C, margin, legacy ? 1 : 0, alpha,
+                       da, db);
+  else
+    hipLaunchKernelGGL(k_contrastive_bwd<false>, dim3(blocks), dim3(TPB), 0,
+                       s, a, b, sim, dist_sq, N, C, margin, legacy ? 1 : 0,
+                       alpha, da, db);
+  ktrace(kContrastiveBwd, wave ? kVarRowWave : kVarRowThread, N, C, blocks);
+}
+
 // ------------------------------------------------------- row/col sums
 __global__ void k_colsum(const float* __restrict__ A, long M, long N,
                          float* __restrict__ out) {
@@ -1910,6 +2069,47 @@ void solver_update_segmented(hipStream_t s, int rule, bool l1, long lo,
   }
 #undef SOLVER_SEG_LAUNCH
   ktrace(kSolverSeg, rule * 2 + (l1 ? 1 : 0), lo, hi, nseg);
+}
+
+// Shared params: one owner layer's arena range [lo, hi) gets the diffs of
+// its blobs' sharers added.  seg_off holds the arena offset of each of the
+// layer's learnable blobs, src_begin[a] .. src_begin[a + 1] bound segment
+// a's sources in srcs (none for a blob nobody shares).  float4 packs in a
+// grid-stride loop, seg_find once per pack, the sources added in table
+// order by the one thread that owns the pack: deterministic, no atomics.
+// A sharer has the owner's count and every blob allocation is padded to 16
+// floats, so a whole pack is loadable from every source; lanes past count
+// add padding to padding.
+__global__ void k_shared_diff_sum(long lo4, long hi4, f4* __restrict__ g_arena,
+                                  const long* __restrict__ seg_off, int nseg,
+                                  const int* __restrict__ src_begin,
+                                  const float* const* __restrict__ srcs) {
+  for (long p = lo4 + blockIdx.x * (long)blockDim.x + threadIdx.x; p < hi4;
+       p += (long)gridDim.x * blockDim.x) {
+    const long i = 4 * p;
+    const int a = seg_find(seg_off, nseg, i);
+    const int s0 = src_begin[a], s1 = src_begin[a + 1];
+    if (s0 == s1) continue;
+    const long off = i - seg_off[a];
+    f4 g = g_arena[p];
+    for (int k = s0; k < s1; ++k) g += *(const f4*)(srcs[k] + off);
+    g_arena[p] = g;
+  }
+}
+void shared_diff_sum(hipStream_t s, long lo, long hi, float* g_arena,
+                     const long* seg_off, int nseg, const int* src_begin,
+                     const float* const* srcs, int nsrc) {
+  CHECK_(lo % 4 == 0 && hi % 4 == 0)
+      << "shared_diff_sum: range [" << lo << ", " << hi
+      << ") is not float4-aligned";
+  if (hi <= lo || nsrc == 0) return;
+  PerfScope perf(PERF_CLASS("shared_diff_sum"), s, 0,
+                 4.0 * (hi - lo) * (2 + nsrc));
+  const long lo4 = lo / 4, hi4 = hi / 4;
+  hipLaunchKernelGGL(k_shared_diff_sum, dim3(nblocks(hi4 - lo4)), dim3(TPB),
+                     0, s, lo4, hi4, (f4*)g_arena, seg_off, nseg, src_begin,
+                     srcs);
+  ktrace(kSharedDiffSum, kVarNone, lo, hi, nseg, nsrc);
 }
 
 // ---------------------------------------------------- LMDB transform

@@ -144,7 +144,8 @@ struct Workspace {
     kSplitK,    // gemm(): split-K partial slabs
     kFlipW,     // conv dgrad: flipped/transposed weights
     kBiasPart,  // bias_grad(): per-slice double partials
-    kLossPart,  // sigmoid_ce_fwd() / euclid_fwd(): per-block double partials
+    kLossPart,  // sigmoid_ce_fwd() / euclid_fwd() / contrastive_fwd():
+                // per-block double partials
     kNumSlots
   };
   void* get(Slot slot, size_t bytes);  // device (GPU mode) / host (CPU mode)
@@ -612,6 +613,60 @@ class EuclideanLossLayer : public Layer {
                     const std::vector<Blob*>&) override;
   float default_loss_weight() const override { return 1.f; }
   bool is_loss_layer() const override { return true; }
+};
+
+// ContrastiveLoss (reference layers/contrastive_loss_layer.cpp/.cu): over
+// a [N][C], b [N][C] and sim [N], Σ_i (sim_i ? d²_i : max(margin - d_i, 0)²)
+// / N / 2 (legacy_version: max(margin - d²_i, 0)).  The rows' d² are kept
+// for the backward; a - b is recomputed there, never stored.
+class ContrastiveLossLayer : public Layer {
+ public:
+  using Layer::Layer;
+  int min_bottom_blobs() const override { return 3; }
+  int max_bottom_blobs() const override { return 3; }
+  void LayerSetUp(const std::vector<Blob*>&,
+                  const std::vector<Blob*>&) override;
+  void Reshape(const std::vector<Blob*>&, const std::vector<Blob*>&) override;
+  void Forward_cpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Forward_gpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Backward_cpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  float default_loss_weight() const override { return 1.f; }
+  bool is_loss_layer() const override { return true; }
+  float margin_ = 1.f;
+  bool legacy_ = false;
+  std::vector<float> dist_sq_;  // CPU mode: d² per row
+  DeviceBuf dist_sq_dev_;       // GPU mode: the same, N floats
+};
+
+// Slice (reference layers/slice_layer.cpp): one bottom cut along an axis
+// into the tops, at slice_point or evenly.  Each top is the Concat backward
+// form of the bottom ([outer][C_t][inner] out of [outer][C][inner] at an
+// offset) and the backward is the Concat forward form, so the GPU paths
+// reuse those two kernels.
+class SliceLayer : public Layer {
+ public:
+  using Layer::Layer;
+  int max_top_blobs() const override { return 4096; }
+  void LayerSetUp(const std::vector<Blob*>&,
+                  const std::vector<Blob*>&) override;
+  void Reshape(const std::vector<Blob*>&, const std::vector<Blob*>&) override;
+  void Forward_cpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Forward_gpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Backward_cpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  int axis_ = 1;
+  std::vector<int> points_;  // slice_point
+  int outer_ = 0, C_ = 0;    // bottom as [outer_][C_][inner_]
+  long inner_ = 0;
 };
 
 // Flatten (reference layers/flatten_layer.cpp): axes [axis, end_axis]

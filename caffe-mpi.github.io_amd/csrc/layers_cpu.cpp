@@ -1280,6 +1280,181 @@ void EuclideanLossLayer::Backward_cpu(const std::vector<Blob*>&,
   }
 }
 
+// -------------------------------------------------------- ContrastiveLoss
+void ContrastiveLossLayer::LayerSetUp(const std::vector<Blob*>&,
+                                      const std::vector<Blob*>&) {
+  if (auto cp = param_->sub("contrastive_loss_param")) {
+    margin_ = (float)cp->num("margin", 1.0);
+    legacy_ = cp->boolean("legacy_version", false);
+  }
+  // sim is a label: it never gets a gradient, whatever propagate_down says
+  // (the reference's backward only loops over the first two bottoms)
+}
+
+void ContrastiveLossLayer::Reshape(const std::vector<Blob*>& bottom,
+                                   const std::vector<Blob*>& top) {
+  // contrastive_loss_layer.cpp:13-20
+  const char* const which[] = {"first", "second", "similarity"};
+  CHECK_EQ_(bottom[0]->channels(), bottom[1]->channels())
+      << "ContrastiveLoss layer '" << name()
+      << "': the two feature inputs must have the same channels";
+  CHECK_EQ_(bottom[0]->num(), bottom[1]->num())
+      << "ContrastiveLoss layer '" << name()
+      << "': the two feature inputs must have the same num";
+  for (int k = 0; k < 3; ++k)
+    CHECK_(bottom[k]->height() == 1 && bottom[k]->width() == 1 &&
+           bottom[k]->count() ==
+               (long)bottom[k]->num() * bottom[k]->channels())
+        << "ContrastiveLoss layer '" << name() << "': the " << which[k]
+        << " input must be [N][C] (trailing dims 1), got "
+        << bottom[k]->shape_string();
+  CHECK_EQ_(bottom[2]->channels(), 1)
+      << "ContrastiveLoss layer '" << name()
+      << "': the similarity input must have one channel";
+  CHECK_EQ_(bottom[2]->count(), (long)bottom[0]->num())
+      << "ContrastiveLoss layer '" << name()
+      << "': the similarity input must hold one value per row";
+  top[0]->Reshape({1});
+}
+
+void ContrastiveLossLayer::Forward_cpu(const std::vector<Blob*>& bottom,
+                                       const std::vector<Blob*>& top) {
+  const float* a = bottom[0]->cpu_data();
+  const float* b = bottom[1]->cpu_data();
+  const float* sim = bottom[2]->cpu_data();
+  const int N = bottom[0]->num(), C = bottom[0]->channels();
+  dist_sq_.resize(N);
+  double loss = 0;
+  for (int i = 0; i < N; ++i) {
+    double s = 0;
+    for (int c = 0; c < C; ++c) {
+      const float d = a[(long)i * C + c] - b[(long)i * C + c];
+      s += (double)d * (double)d;
+    }
+    dist_sq_[i] = (float)s;
+    loss += (double)contrastive_row_loss(dist_sq_[i], (int)sim[i] != 0,
+                                         margin_, legacy_);
+  }
+  top[0]->mutable_cpu_data()[0] = (float)(loss * (0.5 / N));
+}
+
+void ContrastiveLossLayer::Backward_cpu(const std::vector<Blob*>&,
+                                        const std::vector<bool>& prop_down,
+                                        const std::vector<Blob*>& bottom) {
+  const float* a = bottom[0]->cpu_data();
+  const float* b = bottom[1]->cpu_data();
+  const float* sim = bottom[2]->cpu_data();
+  const int N = bottom[0]->num(), C = bottom[0]->channels();
+  CHECK_EQ_((int)dist_sq_.size(), N) << "Backward before Forward";
+  for (int k = 0; k < 2; ++k) {
+    if (!prop_down[k]) continue;
+    const float alpha = (k == 0 ? 1.f : -1.f) * (loss(0) / (float)N);
+    float* d = bottom[k]->mutable_cpu_diff();
+    for (int i = 0; i < N; ++i) {
+      const float coef = contrastive_row_beta(dist_sq_[i], (int)sim[i] != 0,
+                                              margin_, legacy_, alpha);
+      for (int c = 0; c < C; ++c) {
+        const long j = (long)i * C + c;
+        d[j] = coef == 0.f ? 0.f : coef * (a[j] - b[j]);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- Slice
+void SliceLayer::LayerSetUp(const std::vector<Blob*>&,
+                            const std::vector<Blob*>&) {
+  points_.clear();
+  if (auto sp = param_->sub("slice_param")) {
+    CHECK_(!(sp->has("axis") && sp->has("slice_dim")))
+        << "Slice layer '" << name()
+        << "': either axis or slice_dim should be specified; not both";
+    for (long p : sp->inums("slice_point")) points_.push_back((int)p);
+  }
+}
+
+void SliceLayer::Reshape(const std::vector<Blob*>& bottom,
+                         const std::vector<Blob*>& top) {
+  const int axes = bottom[0]->num_axes();
+  auto sp = param_->sub("slice_param");
+  if (sp && sp->has("slice_dim")) {
+    axis_ = (int)sp->inum("slice_dim");
+    CHECK_(axis_ >= 0 && axis_ < axes)
+        << "Slice layer '" << name() << "': slice_dim " << axis_
+        << " out of range for a " << axes << "-axis bottom";
+  } else {
+    axis_ = sp ? (int)sp->inum("axis", 1) : 1;
+    CHECK_(axis_ >= -axes && axis_ < axes)
+        << "Slice layer '" << name() << "': axis " << axis_
+        << " out of range for a " << axes << "-axis bottom";
+    if (axis_ < 0) axis_ += axes;
+  }
+  for (auto* t : top)
+    CHECK_(t != bottom[0])
+        << "Slice layer '" << name() << "' does not run in-place";
+  C_ = bottom[0]->shape(axis_);
+  outer_ = (int)bottom[0]->count(0, axis_);
+  inner_ = bottom[0]->count(axis_ + 1);
+  const int T = (int)top.size();
+  std::vector<int> sizes;
+  if (!points_.empty()) {
+    CHECK_EQ_((int)points_.size(), T - 1)
+        << "Slice layer '" << name() << "': " << T << " tops need " << T - 1
+        << " slice_point entries";
+    int prev = 0;
+    for (int p : points_) {
+      CHECK_(p > prev) << "Slice layer '" << name() << "': slice_point " << p
+                       << " must be greater than " << prev
+                       << " (points strictly increasing, above 0)";
+      CHECK_(p < C_) << "Slice layer '" << name() << "': slice_point " << p
+                     << " is outside the sliced axis of size " << C_;
+      sizes.push_back(p - prev);
+      prev = p;
+    }
+    sizes.push_back(C_ - prev);
+  } else {
+    CHECK_(C_ % T == 0) << "Slice layer '" << name() << "': number of tops ("
+                        << T << ") should evenly divide the sliced axis ("
+                        << C_ << ")";
+    sizes.assign(T, C_ / T);
+  }
+  std::vector<int> shape = bottom[0]->shape();
+  for (int t = 0; t < T; ++t) {
+    shape[axis_] = sizes[t];
+    if (top[t]->shape() != shape) top[t]->Reshape(shape);
+  }
+}
+
+void SliceLayer::Forward_cpu(const std::vector<Blob*>& bottom,
+                             const std::vector<Blob*>& top) {
+  const float* x = bottom[0]->cpu_data();
+  int off = 0;
+  for (auto* t : top) {
+    const int Ct = t->shape(axis_);
+    float* y = t->mutable_cpu_data();
+    for (int n = 0; n < outer_; ++n)
+      memcpy(y + (long)n * Ct * inner_, x + ((long)n * C_ + off) * inner_,
+             sizeof(float) * Ct * inner_);
+    off += Ct;
+  }
+}
+
+void SliceLayer::Backward_cpu(const std::vector<Blob*>& top,
+                              const std::vector<bool>& prop_down,
+                              const std::vector<Blob*>& bottom) {
+  if (!prop_down[0]) return;
+  float* dx = bottom[0]->mutable_cpu_diff();
+  int off = 0;
+  for (auto* t : top) {
+    const int Ct = t->shape(axis_);
+    const float* dy = t->cpu_diff();
+    for (int n = 0; n < outer_; ++n)
+      memcpy(dx + ((long)n * C_ + off) * inner_, dy + (long)n * Ct * inner_,
+             sizeof(float) * Ct * inner_);
+    off += Ct;
+  }
+}
+
 // ---------------------------------------------------------------- Flatten
 void FlattenLayer::Reshape(const std::vector<Blob*>& bottom,
                            const std::vector<Blob*>& top) {
@@ -1346,6 +1521,8 @@ REGISTER_LAYER("Sigmoid", SigmoidLayer)
 REGISTER_LAYER("SigmoidCrossEntropyLoss", SigmoidCrossEntropyLossLayer)
 REGISTER_LAYER("EuclideanLoss", EuclideanLossLayer)
 REGISTER_LAYER("Flatten", FlattenLayer)
+REGISTER_LAYER("ContrastiveLoss", ContrastiveLossLayer)
+REGISTER_LAYER("Slice", SliceLayer)
 // ---------------------------------------------------------------- Scale
 // Reference layers/scale_layer.cpp (+ bias inside, :121-134): channel-wise
 // y = x * scale[c] (+ bias[c]); the BVLC BatchNorm+Scale prototxt pattern.

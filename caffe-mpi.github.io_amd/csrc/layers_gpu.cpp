@@ -684,4 +684,59 @@ void EuclideanLossLayer::Backward_gpu(const std::vector<Blob*>&,
       prop_down[1] ? bottom[1]->mutable_gpu_diff() : nullptr);
 }
 
+// -------------------------------------------------------- ContrastiveLoss
+void ContrastiveLossLayer::Forward_gpu(const std::vector<Blob*>& bottom,
+                                       const std::vector<Blob*>& top) {
+  const int N = bottom[0]->num(), C = bottom[0]->channels();
+  double* partials = (double*)Workspace::get_global().get(
+      Workspace::kLossPart, sizeof(double) * gpu::contrastive_partials(N, C));
+  gpu::contrastive_fwd(Engine::get().stream, bottom[0]->gpu_data(),
+                       bottom[1]->gpu_data(), bottom[2]->gpu_data(), N, C,
+                       margin_, legacy_,
+                       (float*)dist_sq_dev_.reserve(sizeof(float) * N),
+                       partials, top[0]->mutable_gpu_data());
+}
+
+void ContrastiveLossLayer::Backward_gpu(const std::vector<Blob*>&,
+                                        const std::vector<bool>& prop_down,
+                                        const std::vector<Blob*>& bottom) {
+  if (!prop_down[0] && !prop_down[1]) return;
+  const int N = bottom[0]->num(), C = bottom[0]->channels();
+  CHECK_GE_(dist_sq_dev_.bytes, sizeof(float) * N) << "Backward before Forward";
+  gpu::contrastive_bwd(
+      Engine::get().stream, bottom[0]->gpu_data(), bottom[1]->gpu_data(),
+      bottom[2]->gpu_data(), (const float*)dist_sq_dev_.p, N, C, margin_,
+      legacy_, loss(0) / (float)N,
+      prop_down[0] ? bottom[0]->mutable_gpu_diff() : nullptr,
+      prop_down[1] ? bottom[1]->mutable_gpu_diff() : nullptr);
+}
+
+// ---------------------------------------------------------------- Slice
+void SliceLayer::Forward_gpu(const std::vector<Blob*>& bottom,
+                             const std::vector<Blob*>& top) {
+  Engine& E = Engine::get();
+  const float* x = bottom[0]->gpu_data();
+  int off = 0;
+  for (auto* t : top) {
+    const int Ct = t->shape(axis_);
+    gpu::concat_bwd(E.stream, x, outer_, Ct, inner_, C_, off,
+                    t->mutable_gpu_data());
+    off += Ct;
+  }
+}
+
+void SliceLayer::Backward_gpu(const std::vector<Blob*>& top,
+                              const std::vector<bool>& prop_down,
+                              const std::vector<Blob*>& bottom) {
+  if (!prop_down[0]) return;
+  Engine& E = Engine::get();
+  float* dx = bottom[0]->mutable_gpu_diff();
+  int off = 0;
+  for (auto* t : top) {
+    const int Ct = t->shape(axis_);
+    gpu::concat_fwd(E.stream, t->gpu_diff(), outer_, Ct, inner_, C_, off, dx);
+    off += Ct;
+  }
+}
+
 }  // namespace camd

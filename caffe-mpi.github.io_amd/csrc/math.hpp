@@ -114,6 +114,34 @@ CAMD_HD inline float sigmoid_ce_term(float x, float t) {
   return logf(1.f + expf(x - 2.f * x * pos)) - x * (t - pos);
 }
 
+// -------------------------------------------------------- contrastive loss
+// Per-row formulas of the reference's contrastive_loss_layer.cpp:45-58 and
+// :86-105, shared by the CPU loops and the GPU kernels.  dsq is the row's
+// Σ (a - b)².  sqrtf is the IEEE form and the clamps are written as
+// comparisons (not fmaxf, which drops a NaN operand), so both modes take
+// the same branch and a NaN row gives a NaN loss.
+CAMD_HD inline float contrastive_row_loss(float dsq, bool similar,
+                                          float margin, bool legacy) {
+  if (similar) return dsq;
+  if (legacy) {
+    const float m = margin - dsq;
+    return m < 0.f ? 0.f : m;
+  }
+  const float m = margin - sqrtf(dsq);
+  return m < 0.f ? 0.f : m * m;
+}
+// the factor of (a - b) in the row's gradient, alpha = sign * loss_weight / N
+// (0 for a dissimilar row at or outside the margin)
+CAMD_HD inline float contrastive_row_beta(float dsq, bool similar,
+                                          float margin, bool legacy,
+                                          float alpha) {
+  if (similar) return alpha;
+  if (legacy) return margin - dsq > 0.f ? -alpha : 0.f;
+  const float d = sqrtf(dsq);
+  const float mdist = margin - d;
+  return mdist > 0.f ? -alpha * mdist / (d + 1e-4f) : 0.f;
+}
+
 // --------------------------------------------------------- exact fast division
 // n / d for 0 <= n < 2^31 and 1 <= d <= 2^31 as multiply-high, add and shift
 // (Granlund & Montgomery's round-up form: with l = ceil(log2 d) and
@@ -228,6 +256,10 @@ void gemm_trace_readers(long* cursor, long* wide64);
 //       blocks=<grid> passes=<grid-stride passes of the busiest thread>
 //   op=sigmoid_ce_fwd|euclid_fwd n=<elements> blocks=<grid>
 //       partials=<doubles the final sum adds> passes=<as above>
+//   op=shared_diff_sum lo=<arena lo> hi=<arena hi> nseg=<the owner layer's
+//       learnable blobs> nsrc=<sharing blobs added>
+//   op=contrastive_fwd|contrastive_bwd var=row_thread|row_wave N=<rows>
+//       C=<row width> blocks=<grid>
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
 
@@ -340,6 +372,23 @@ void euclid_fwd(hipStream_t s, const float* a, const float* b, long n,
 void euclid_bwd(hipStream_t s, const float* a, const float* b, long n,
                 float scale_a, float* da, float scale_b, float* db);
 
+// ContrastiveLoss over a [N][C], b [N][C], sim [N]: the forward writes each
+// row's d² into dist_sq (N floats, kept by the layer for the backward) and
+// Σ contrastive_row_loss / N / 2 into loss_out through `partials`
+// (contrastive_partials(N, C) doubles); the backward recomputes a - b and
+// writes da = beta·(a - b) and/or db = -beta·(a - b) (null = not wanted),
+// beta = contrastive_row_beta(.., alpha), alpha = loss_weight / N.  One
+// thread per row for narrow rows, one wave per row for wide ones.
+int contrastive_partials(int N, int C);
+void contrastive_fwd(hipStream_t s, const float* a, const float* b,
+                     const float* sim, int N, int C, float margin,
+                     bool legacy, float* dist_sq, double* partials,
+                     float* loss_out);
+void contrastive_bwd(hipStream_t s, const float* a, const float* b,
+                     const float* sim, const float* dist_sq, int N, int C,
+                     float margin, bool legacy, float alpha, float* da,
+                     float* db);
+
 // out[n] = Σ_m A[m][n] — IP bias grad (deterministic)
 void colsum(hipStream_t s, const float* A, long M, long N, float* out);
 
@@ -385,6 +434,15 @@ void solver_update_segmented(hipStream_t s, int rule, bool l1, long lo,
                              float* const* w_ptrs, const float* lr_mults,
                              const float* decay_mults, int nseg,
                              const SolverCoef& coef);
+
+// Shared params (Net::plan_param_sharing): add the sharers' diffs into one
+// owner layer's padded arena range [lo, hi), multiples of 4.  seg_off: the
+// arena offsets of the layer's nseg learnable blobs; src_begin: nseg + 1
+// bounds into srcs, the sharers' diff pointers (nsrc of them in the range);
+// tables uploaded once at net build.  Fixed order, no atomics.
+void shared_diff_sum(hipStream_t s, long lo, long hi, float* g_arena,
+                     const long* seg_off, int nseg, const int* src_begin,
+                     const float* const* srcs, int nsrc);
 
 // LMDB batch transform: uint8 -> fp32 crop/mirror/mean/scale
 // (data_transformer.cu:14-100 analog); geo = per-image (ho, wo, mirror),

@@ -133,6 +133,8 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
   name_ = msg->str("name");
   for (auto& lm : filter_layers(*msg)) append_layer(lm, batch_override);
   set_backward_flags(msg->boolean("force_backward", false));
+  param_sharing_ = plan_param_sharing();
+  apply_param_sharing();
   collect_params();
   fusions_ = plan_fusions();
   diff_sharing_ = plan_diff_sharing();
@@ -141,6 +143,7 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
     apply_diff_sharing();
     setup_arena();
   }
+  setup_shared_sums();
 }
 
 // the layers of this net's state, with Splits inserted
@@ -254,18 +257,109 @@ void Net::set_backward_flags(bool force) {
   }
 }
 
-// learnable params in backward-completion order (reverse layer order)
+// ----------------------------------------------------- param-sharing plan
+// reference Net::AppendParam (net.cpp:576-667).  The first blob whose
+// ParamSpec carries a name owns the name; a later blob of that name, in any
+// layer of any type, is a sharer.  Shapes must agree (share_mode STRICT,
+// the default) or counts (PERMISSIVE, read from the sharer's spec as the
+// reference does); lr_mult / decay_mult given on both sides must agree, and
+// a side that gives none adopts the other's.
+std::vector<Net::ParamShare> Net::plan_param_sharing() const {
+  struct Owner {
+    int layer, blob;
+    bool has_lr, has_decay;
+    float lr, decay;
+  };
+  std::map<std::string, Owner> owners;
+  std::vector<ParamShare> plan;
+  for (int i = 0; i < (int)layers_.size(); ++i) {
+    const auto specs = layers_[i]->param()->subs("param");
+    auto& lb = layers_[i]->blobs();
+    for (int j = 0; j < (int)lb.size() && j < (int)specs.size(); ++j) {
+      const PMsg& sp = *specs[j];
+      const std::string name = sp.str("name");
+      if (name.empty()) continue;
+      const float lr = (float)sp.num("lr_mult", 1.0);
+      const float decay = (float)sp.num("decay_mult", 1.0);
+      auto it = owners.find(name);
+      if (it == owners.end()) {
+        owners[name] = {i, j, sp.has("lr_mult"), sp.has("decay_mult"), lr,
+                        decay};
+        continue;
+      }
+      Owner& o = it->second;
+      Blob& mine = *lb[j];
+      Blob& theirs = *layers_[o.layer]->blobs()[o.blob];
+      std::ostringstream who;
+      who << "param '" << name << "' owned by layer '"
+          << layers_[o.layer]->name() << "' with layer '"
+          << layers_[i]->name() << "'";
+      if (sp.str("share_mode", "STRICT") == "PERMISSIVE") {
+        if (mine.count() != theirs.count())
+          CAMD_FATAL << "Cannot share " << who.str()
+                     << "; count mismatch.  Owner layer param shape is "
+                     << theirs.shape_string() << "; sharing layer shape is "
+                     << mine.shape_string();
+      } else if (mine.shape() != theirs.shape()) {
+        CAMD_FATAL << "Cannot share " << who.str()
+                   << "; shape mismatch.  Owner layer param shape is "
+                   << theirs.shape_string()
+                   << "; sharing layer expects shape " << mine.shape_string();
+      }
+      if (sp.has("lr_mult")) {
+        if (o.has_lr && o.lr != lr)
+          CAMD_FATAL << "Cannot share " << who.str()
+                     << "; mismatched lr_mult (" << o.lr << " vs " << lr
+                     << ")";
+        o.has_lr = true;
+        o.lr = lr;
+      }
+      if (sp.has("decay_mult")) {
+        if (o.has_decay && o.decay != decay)
+          CAMD_FATAL << "Cannot share " << who.str()
+                     << "; mismatched decay_mult (" << o.decay << " vs "
+                     << decay << ")";
+        o.has_decay = true;
+        o.decay = decay;
+      }
+      plan.push_back({i, j, name, o.layer, o.blob, o.lr, o.decay});
+    }
+  }
+  return plan;
+}
+
+// a sharer's blob uses the owner's data memory for the life of the net; its
+// diff stays its own
+void Net::apply_param_sharing() {
+  for (auto& s : param_sharing_)
+    layers_[s.layer]->blobs()[s.blob]->ShareData(
+        *layers_[s.owner_layer]->blobs()[s.owner_blob]);
+}
+
+// learnable params in backward-completion order (reverse layer order);
+// sharers are none (reference learnable_params_)
 void Net::collect_params() {
+  std::map<std::pair<int, int>, const ParamShare*> sharer, last_share;
+  for (auto& s : param_sharing_) {
+    sharer[{s.layer, s.blob}] = &s;
+    last_share[{s.owner_layer, s.owner_blob}] = &s;  // the merged multipliers
+  }
   for (int i = (int)layers_.size() - 1; i >= 0; --i) {
     auto& lb = layers_[i]->blobs();
     for (size_t j = 0; j < lb.size(); ++j) {
       if (layers_[i]->skip_apply_update((int)j)) continue;
+      if (sharer.count({i, (int)j})) continue;
       LParam p;
       p.blob = lb[j].get();
       p.layer = layers_[i].get();
       p.blob_idx = (int)j;
       p.lr_mult = layers_[i]->lr_mult((int)j);
       p.decay_mult = layers_[i]->decay_mult((int)j);
+      auto own = last_share.find({i, (int)j});
+      if (own != last_share.end()) {
+        p.lr_mult = own->second->lr_mult;
+        p.decay_mult = own->second->decay_mult;
+      }
       p.count = p.blob->count();
       p.offset = arena_count_;
       arena_count_ += (long)padded(p.count);
@@ -460,6 +554,90 @@ void Net::setup_arena() {
     HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
 }
 
+// What Backward adds after each owner layer: the sharers of the layer's
+// learnable blobs, in plan order (a shared statistics blob shares data only
+// and has no gradient to add).  GPU mode: one launch per owner layer over
+// the layer's padded arena range, so the tables hold one segment per
+// learnable blob of the layer (with or without sharers) and the sharers'
+// diff pointers by segment; uploaded once, synchronously, like the solver's
+// segment table.  The pointers stay good: no param blob is reshaped after
+// the build.
+void Net::setup_shared_sums() {
+  if (param_sharing_.empty()) return;
+  std::map<const Blob*, bool> learnable;
+  for (auto& p : params_) learnable[p.blob] = true;
+  for (auto& s : param_sharing_) {
+    Blob* owner = layers_[s.owner_layer]->blobs()[s.owner_blob].get();
+    if (!learnable.count(owner)) continue;
+    shared_sums_[s.owner_layer].srcs.push_back(
+        {owner, layers_[s.layer]->blobs()[s.blob].get()});
+  }
+  if (Engine::get().mode != Mode::GPU || shared_sums_.empty()) return;
+  std::vector<long> seg_off;
+  std::vector<int> src_begin;
+  std::vector<const float*> srcs;
+  for (auto& kv : shared_sums_) {
+    SharedSum& ss = kv.second;
+    ss.seg_start = (int)seg_off.size();
+    bool first = true;
+    for (auto& p : params_) {  // a layer's params: consecutive, ascending
+      if (p.layer != layers_[kv.first].get()) continue;
+      if (first) ss.lo = p.offset;
+      first = false;
+      ss.hi = p.offset + (long)padded(p.count);
+      seg_off.push_back(p.offset);
+      src_begin.push_back((int)srcs.size());
+      for (auto& src : ss.srcs)
+        if (src.owner == p.blob) srcs.push_back(src.sharer->mutable_gpu_diff());
+    }
+    ss.nseg = (int)seg_off.size() - ss.seg_start;
+  }
+  src_begin.push_back((int)srcs.size());  // the one closing bound
+  sum_nseg_ = seg_off.size();
+  sum_nsrc_ = srcs.size();
+  Engine& E = Engine::get();
+  d_sum_seg_off_ = (long*)E.dalloc.alloc(seg_off.size() * sizeof(long));
+  d_sum_src_begin_ = (int*)E.dalloc.alloc(src_begin.size() * sizeof(int));
+  d_sum_srcs_ = (const float**)E.dalloc.alloc(srcs.size() * sizeof(float*));
+  HIP_CHECK(hipMemcpy(d_sum_seg_off_, seg_off.data(),
+                      seg_off.size() * sizeof(long), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_sum_src_begin_, src_begin.data(),
+                      src_begin.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_sum_srcs_, srcs.data(), srcs.size() * sizeof(float*),
+                      hipMemcpyHostToDevice));
+}
+
+// The sum tables go back to the caching allocator, which may hand them to
+// the next net: wait for the last launch that reads them first.
+Net::~Net() {
+  if (!d_sum_seg_off_) return;
+  Engine& E = Engine::get();
+  (void)hipStreamSynchronize(E.stream);
+  E.dalloc.release(d_sum_seg_off_, sum_nseg_ * sizeof(long));
+  E.dalloc.release(d_sum_src_begin_, (sum_nseg_ + 1) * sizeof(int));
+  E.dalloc.release(d_sum_srcs_, sum_nsrc_ * sizeof(float*));
+}
+
+// Layer backwards overwrite their param diffs, so a sharer writes its own
+// diff and the owner's gets the sum here.  Owners come first in layer order:
+// when the owner layer's backward has run, every sharer's has.
+void Net::sum_shared_diffs(int i) {
+  auto it = shared_sums_.find(i);
+  if (it == shared_sums_.end()) return;
+  const SharedSum& ss = it->second;
+  Engine& E = Engine::get();
+  if (E.mode == Mode::GPU) {
+    gpu::shared_diff_sum(E.stream, ss.lo, ss.hi, diff_arena_,
+                         d_sum_seg_off_ + ss.seg_start, ss.nseg,
+                         d_sum_src_begin_ + ss.seg_start, d_sum_srcs_,
+                         (int)ss.srcs.size());
+  } else {
+    for (auto& src : ss.srcs)
+      cpu::axpy(src.owner->count(), 1.f, src.sharer->cpu_diff(),
+                src.owner->mutable_cpu_diff());
+  }
+}
+
 void Net::forward_layer(size_t i) {
   LayerScope scope(*layers_[i], "Forward");
   layers_[i]->Forward(bottoms_[i], tops_[i]);
@@ -481,6 +659,7 @@ void Net::Backward(ReduceHook* hook) {
   hipEvent_t last_ev = nullptr;
   for (int i = (int)layers_.size() - 1; i >= 0; --i) {
     if (layer_need_bwd_[i]) backward_layer(i);
+    if (!shared_sums_.empty()) sum_shared_diffs(i);
     if (hook) {
       // emit this layer's params (consecutive in params_, ascending offset)
       const size_t start = pidx;

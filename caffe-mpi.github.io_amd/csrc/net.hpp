@@ -150,6 +150,27 @@ class Net {
   // in layer order, then bottom order
   const std::vector<DiffShare>& diff_sharing() const { return diff_sharing_; }
 
+  // Named param blobs (reference Net::AppendParam, net.cpp:576-667): the
+  // first blob of a name owns it, every later one is a sharer.  A sharer
+  // uses the owner's data memory, is no learnable param, and keeps a diff
+  // of its own that Backward adds into the owner's right after the owner
+  // layer's backward.  Planned from the built layers in both modes.
+  struct ParamShare {
+    int layer, blob;              // the sharer
+    std::string name;             // the ParamSpec name
+    int owner_layer, owner_blob;  // the first blob of that name
+    // the owner's multipliers once this sharer's spec is merged in: a side
+    // that does not set one adopts the other side's
+    float lr_mult, decay_mult;
+  };
+  // in layer order, then blob order
+  const std::vector<ParamShare>& param_sharing() const {
+    return param_sharing_;
+  }
+  ~Net();
+  Net(const Net&) = delete;
+  Net& operator=(const Net&) = delete;
+
  private:
   // the net build, in order; each step reads and writes the members below
   void init(const PMsgPtr& msg, int batch_override);
@@ -157,12 +178,15 @@ class Net {
   void insert_splits(std::vector<PMsgPtr>& layer_msgs);
   void append_layer(const PMsgPtr& layer_msg, int batch_override);
   void set_backward_flags(bool force_backward);
+  std::vector<ParamShare> plan_param_sharing() const;
+  void apply_param_sharing();
   void collect_params();
   std::vector<Fusion> plan_fusions() const;
   void apply_fusions();
   std::vector<DiffShare> plan_diff_sharing() const;
   void apply_diff_sharing();
   void setup_arena();
+  void setup_shared_sums();
 
   // the graph predicates the two plans are made of
   bool in_place(int i) const {
@@ -187,6 +211,8 @@ class Net {
   // one layer's dispatch under its error scope
   void forward_layer(size_t i);
   void backward_layer(size_t i);
+  // owner layer i: add its sharers' diffs into its own (no-op elsewhere)
+  void sum_shared_diffs(int i);
 
   std::string name_;
   Phase phase_;
@@ -200,6 +226,29 @@ class Net {
   std::vector<LParam> params_;
   std::vector<Fusion> fusions_;
   std::vector<DiffShare> diff_sharing_;
+  std::vector<ParamShare> param_sharing_;
+  // What sum_shared_diffs runs for one owner layer: the sharers of its
+  // learnable blobs in plan order and, in GPU mode, the layer's arena range
+  // and its slice of the device tables (uploaded once at build).
+  struct SharedSum {
+    struct Src {
+      Blob* owner;
+      Blob* sharer;
+    };
+    std::vector<Src> srcs;
+    long lo = 0, hi = 0;          // padded arena range of the layer's params
+    int seg_start = 0, nseg = 0;  // into d_sum_seg_off_ / d_sum_src_begin_
+  };
+  std::map<int, SharedSum> shared_sums_;  // by owner layer index
+  // Device tables, returned to the allocator in ~Net.  The segments of all
+  // owner layers stand one after another, in owner-layer order, and so do
+  // their sources: segment k's sources are srcs[src_begin[k] ..
+  // src_begin[k + 1]), with ONE closing bound after the last segment of the
+  // last layer (a layer's slice starts at its seg_start in both tables).
+  long* d_sum_seg_off_ = nullptr;       // arena offset of every segment
+  int* d_sum_src_begin_ = nullptr;      // segments + 1 source bounds
+  const float** d_sum_srcs_ = nullptr;  // the sharers' diff pointers
+  size_t sum_nseg_ = 0, sum_nsrc_ = 0;  // entries: segments, sources
   long arena_count_ = 0;
   float* diff_arena_ = nullptr;
   std::vector<hipEvent_t> layer_events_;

@@ -221,6 +221,14 @@ static int run_train_rank(std::map<std::string, std::string> flags, int dev,
   }
   Solver solver(sp, batch_override);
   if (grank == 0) fprintf(stderr, "Solver type: %s\n", solver.type());
+  // the reference's Net::AppendParam line, once per sharing param blob
+  for (auto& s : solver.net().param_sharing())
+    if (grank == 0)
+      fprintf(stderr,
+              "Sharing parameters '%s' owned by layer '%s', param index %d\n",
+              s.name.c_str(),
+              solver.net().layers()[s.owner_layer]->name().c_str(),
+              s.owner_blob);
   solver.set_action_request(&action_request);
   if (grank != 0) solver.set_snapshot_enabled(false);
   if (gworld > 1) {

@@ -206,7 +206,14 @@ int caffe_gemm_trace_readers(long* cursor, long* wide64);
  * "op=lrn_fwd var=ring5 odd=1", "op=softmax_fwd rows=8450 C=3 blocks=2048",
  * "op=sgd_seg lo=0 hi=272 nseg=6"; the segmented update of the other solver
  * rules (and SGD with L1) records
- * "op=solver_seg rule=adam reg=L2 lo=0 hi=272 nseg=6". */
+ * "op=solver_seg rule=adam reg=L2 lo=0 hi=272 nseg=6".  The sum of shared
+ * params' gradients into their owner layer's arena range records
+ * "op=shared_diff_sum lo=0 hi=32 nseg=2 nsrc=2" (segments = the owner
+ * layer's learnable blobs, sources = the sharing blobs), and the
+ * ContrastiveLoss kernels record
+ * "op=contrastive_fwd var=row_thread N=64 C=2 blocks=1" and
+ * "op=contrastive_bwd var=row_wave N=3 C=257 blocks=1" (one thread or one
+ * wave per row). */
 int caffe_kernel_trace(int enable);
 int caffe_kernel_trace_read(char* buf, int cap);
 /* The graph fusions planned for a net at build time, same buffer contract
@@ -229,6 +236,16 @@ int caffe_net_fusions(caffe_net_t net, char* buf, int cap);
  * and gets one copy.  The same in CPU mode, where every such bottom is
  * copied. */
 int caffe_net_diff_sharing(caffe_net_t net, char* buf, int cap);
+/* The shared params of a net (reference Net::AppendParam, net.cpp:576-667),
+ * planned at build time and read like the two plans above: one line
+ * "layer blob_idx name owner_layer owner_blob_idx" per sharer, in layer
+ * order, then blob order.  The first param blob whose ParamSpec carries
+ * `name` owns it; every later blob of that name shares the owner's weights
+ * (share_mode STRICT: equal shapes, PERMISSIVE: equal counts), is no
+ * learnable param (caffe_net_num_params counts owners only) and has its
+ * gradient added into the owner's right after the owner layer's backward.
+ * The same in CPU mode. */
+int caffe_net_param_sharing(caffe_net_t net, char* buf, int cap);
 /* Self-test of the exact fast division the GEMM staging decomposes its view
  * indices with (host code, no GPU): for every divisor in [d_lo, d_hi]
  * compares quotient and remainder with / and % over the dividends 0..2^20,

@@ -12,7 +12,8 @@ reference's convert_imageset output (keys "%08d_x", sorted).
 Usage:
   python tools/make_lmdb.py OUT_DIR N C H W [seed]
 Records are deterministic uint8 images keyed by (seed, index) and labels
-index % 10 — tests regenerate and independently predict the bytes.
+index % 10 (make_lmdb(..., label_mod=k): index % k) — tests regenerate and
+independently predict the bytes.
 """
 import os
 import struct
@@ -171,12 +172,14 @@ class Writer:
             f.write(out)
 
 
-def make_lmdb(path, n, c, h, w, seed=1234):
+def make_lmdb(path, n, c, h, w, seed=1234, label_mod=10):
+    """label_mod: record i is labelled i % label_mod (2 gives the 0 / 1
+    similarity labels of a siamese pair database)."""
     w_ = Writer()
     items = []  # (key, payload) in sorted key order
     for i in range(n):
         key = b"%08d" % i
-        val = datum(c, h, w, record_bytes(seed, i, c, h, w), i % 10)
+        val = datum(c, h, w, record_bytes(seed, i, c, h, w), i % label_mod)
         items.append((key, val))
     # leaf capacity: node 8 + klen + dlen (pad to even); spill big values
     leaves = []
