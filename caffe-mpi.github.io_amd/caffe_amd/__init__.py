@@ -110,6 +110,9 @@ _lib.caffe_solver_type.restype = ctypes.c_char_p
 _lib.caffe_solver_history_slots.argtypes = [_vp]
 _lib.caffe_solver_history.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _f32p,
                                       ctypes.c_long]
+_lib.caffe_solver_clip_gradients.argtypes = [_vp]
+_lib.caffe_solver_clip_gradients.restype = ctypes.c_float
+_lib.caffe_solver_grad_norm.argtypes = [_vp, _f32p, _f32p]
 
 ALLREDUCE_CB = ctypes.CFUNCTYPE(None, _f32p, ctypes.c_long, ctypes.c_void_p)
 _lib.caffe_comm_set_callback.argtypes = [_vp, ALLREDUCE_CB, ctypes.c_void_p,
@@ -261,7 +264,9 @@ def kernel_trace_read():
     adadelta | adam) and reg (L1 | L2)); shared_diff_sum (the sum of shared
     params' gradients after an owner layer's backward) with lo, hi, nseg,
     nsrc; contrastive_fwd | contrastive_bwd with var (row_thread | row_wave),
-    N, C, blocks."""
+    N, C, blocks.  With clip_gradients set: grad_sumsq (a bucket's sum of
+    squares) with lo, hi, blocks, passes; clip_final with partials; and the
+    sgd_seg / solver_seg records carry clip=1."""
     return _trace_records(_lib.caffe_kernel_trace_read)
 
 
@@ -467,6 +472,21 @@ class Solver:
         _ck(_lib.caffe_solver_history(self._h, slot, i,
                                       out.ctypes.data_as(_f32p), cnt))
         return out
+
+    @property
+    def clip_gradients(self):
+        """SolverParameter.clip_gradients as parsed; negative = off."""
+        return _lib.caffe_solver_clip_gradients(self._h)
+
+    def grad_norm(self):
+        """(norm, factor) of the last finished iteration: the global L2 norm
+        of the reduced gradient over world, and the clip factor applied
+        (1.0 when the norm was within clip_gradients).  Syncs.  An error
+        with clip_gradients off or before the first step."""
+        norm, factor = ctypes.c_float(), ctypes.c_float()
+        _ck(_lib.caffe_solver_grad_norm(self._h, ctypes.byref(norm),
+                                        ctypes.byref(factor)))
+        return np.float32(norm.value), np.float32(factor.value)
 
     def comm_unique_id(self):
         buf = (ctypes.c_uint8 * 128)()

@@ -247,6 +247,14 @@ class SGDSolver:
     def iter(self):
         return self._solver.iter
 
+    @property
+    def clip_gradients(self):
+        return self._solver.clip_gradients
+
+    def grad_norm(self):
+        """(norm, factor) of the last iteration; needs clip_gradients."""
+        return self._solver.grad_norm()
+
 
 class NesterovSolver(SGDSolver):
     _type = "Nesterov"

@@ -231,6 +231,17 @@ int caffe_solver_history(caffe_solver_t s, int slot, int param_index,
   API_CATCH
 }
 
+float caffe_solver_clip_gradients(caffe_solver_t s) {
+  return S(s)->clip_gradients();
+}
+
+int caffe_solver_grad_norm(caffe_solver_t s, float* norm, float* factor) {
+  API_TRY
+  S(s)->grad_norm(norm, factor);
+  return 0;
+  API_CATCH
+}
+
 int caffe_net_save_weights(caffe_net_t n, const char* path) {
   API_TRY
   N(n)->SaveWeights(path);

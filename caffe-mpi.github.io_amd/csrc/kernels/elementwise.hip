@@ -38,7 +38,8 @@ enum KOp {
   kPoolMaxFwd, kPoolMaxBwd, kPoolAveFwd, kPoolAveBwd, kBnFwdStats,
   kBnBwdStats, kLrnFwd, kLrnBwd, kSoftmaxFwd, kSgdSeg, kSolverSeg,
   kSigmoidFwd, kSigmoidBwd, kSigmoidCeFwd, kSigmoidCeBwd, kEuclidFwd,
-  kEuclidBwd, kSharedDiffSum, kContrastiveFwd, kContrastiveBwd
+  kEuclidBwd, kSharedDiffSum, kContrastiveFwd, kContrastiveBwd, kGradSumsq,
+  kClipFinal
 };
 enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
             kVarScalar, kVarRing5, kVarRowThread, kVarRowWave };
@@ -79,7 +80,7 @@ long kernel_trace_read(char* buf, long cap) {
       "softmax_fwd",  "sgd_seg",      "solver_seg",   "sigmoid_fwd",
       "sigmoid_bwd",  "sigmoid_ce_fwd", "sigmoid_ce_bwd", "euclid_fwd",
       "euclid_bwd",   "shared_diff_sum", "contrastive_fwd",
-      "contrastive_bwd"};
+      "contrastive_bwd", "grad_sumsq",  "clip_final"};
   // solver_seg keeps rule * 2 + l1 in the var byte
   static const char* const rule[] = {"sgd",     "nesterov", "adagrad",
                                      "rmsprop", "adadelta", "adam"};
@@ -118,10 +119,20 @@ long kernel_trace_read(char* buf, long cap) {
                      op[r.op], r.a, r.b, r.c);
         break;
       case kSolverSeg:
+        // d: the launch read the clip factor; the unclipped text is unchanged
         n = snprintf(line, sizeof(line),
-                     "op=%s rule=%s reg=%s lo=%ld hi=%ld nseg=%ld\n",
+                     "op=%s rule=%s reg=%s lo=%ld hi=%ld nseg=%ld%s\n",
                      op[r.op], rule[r.var >> 1], (r.var & 1) ? "L1" : "L2",
-                     r.a, r.b, r.c);
+                     r.a, r.b, r.c, r.d ? " clip=1" : "");
+        break;
+      case kGradSumsq:
+        n = snprintf(line, sizeof(line),
+                     "op=%s lo=%ld hi=%ld blocks=%ld passes=%ld\n", op[r.op],
+                     r.a, r.b, r.c, r.d);
+        break;
+      case kClipFinal:
+        n = snprintf(line, sizeof(line), "op=%s partials=%ld\n", op[r.op],
+                     r.a);
         break;
       case kSigmoidFwd:
       case kSigmoidBwd:
@@ -146,9 +157,9 @@ long kernel_trace_read(char* buf, long cap) {
         n = snprintf(line, sizeof(line), "op=%s var=%s N=%ld C=%ld blocks=%ld\n",
                      op[r.op], var[r.var], r.a, r.b, r.c);
         break;
-      default:
-        n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld\n",
-                     op[r.op], r.a, r.b, r.c);
+      default:  // sgd_seg; d as for solver_seg
+        n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld%s\n",
+                     op[r.op], r.a, r.b, r.c, r.d ? " clip=1" : "");
         break;
     }
     if (len + n < cap) memcpy(buf + len, line, (size_t)n + 1);
@@ -1953,6 +1964,19 @@ __device__ __forceinline__ int seg_find(const long* __restrict__ seg_off,
 // MULTIPLIERS (uploaded once — the per-iteration lr/decay ride in as
 // kernel args, so no H2D traffic in the iteration loop).
 // Elements in inter-param padding update harmlessly (their g is 0).
+// The loop is a macro so that k_sgd_seg and its clip_gradients sibling
+// compile from the same text: a shared __device__ function changed the
+// unclipped kernel's registers, and that kernel is the benchmark's.
+#define SGD_SEG_LOOP(GSCALE)                                              \
+  for (long i = lo + blockIdx.x * (long)blockDim.x + threadIdx.x; i < hi; \
+       i += (long)gridDim.x * blockDim.x) {                               \
+    const int a = seg_find(seg_off, nseg, i);                             \
+    float* w = w_ptrs[a] + (i - seg_off[a]);                              \
+    float gi = g_arena[i] * GSCALE + (decay * decay_mults[a]) * *w;       \
+    gi = h_arena[i] = mom * h_arena[i] + (lr * lr_mults[a]) * gi;         \
+    *w -= gi;                                                             \
+    g_arena[i] = 0.f;                                                     \
+  }
 __global__ void k_sgd_seg(long lo, long hi, float* __restrict__ g_arena,
                           float* __restrict__ h_arena,
                           const long* __restrict__ seg_off,
@@ -1960,22 +1984,36 @@ __global__ void k_sgd_seg(long lo, long hi, float* __restrict__ g_arena,
                           const float* __restrict__ lr_mults,
                           const float* __restrict__ decay_mults, int nseg,
                           float mom, float lr, float decay, float gscale) {
-  for (long i = lo + blockIdx.x * (long)blockDim.x + threadIdx.x; i < hi;
-       i += (long)gridDim.x * blockDim.x) {
-    const int a = seg_find(seg_off, nseg, i);
-    float* w = w_ptrs[a] + (i - seg_off[a]);
-    float gi = g_arena[i] * gscale + (decay * decay_mults[a]) * *w;
-    gi = h_arena[i] = mom * h_arena[i] + (lr * lr_mults[a]) * gi;
-    *w -= gi;
-    g_arena[i] = 0.f;
-  }
+  SGD_SEG_LOOP(gscale)
 }
+// clip_gradients: the same update with the iteration's clip factor (written
+// to device memory by k_clip_final) folded into gscale once per thread
+__global__ void k_sgd_seg_clip(long lo, long hi, float* __restrict__ g_arena,
+                               float* __restrict__ h_arena,
+                               const long* __restrict__ seg_off,
+                               float* const* __restrict__ w_ptrs,
+                               const float* __restrict__ lr_mults,
+                               const float* __restrict__ decay_mults, int nseg,
+                               float mom, float lr, float decay, float gscale,
+                               const float* __restrict__ factor) {
+  const float clipped = gscale * factor[0];
+  SGD_SEG_LOOP(clipped)
+}
+#undef SGD_SEG_LOOP
 void sgd_update_segmented(hipStream_t s, long lo, long hi, float* g_arena,
                           float* h_arena, const long* seg_off,
                           float* const* w_ptrs, const float* lr_mults,
                           const float* decay_mults, int nseg, float mom,
-                          float lr, float decay, float gscale) {
+                          float lr, float decay, float gscale,
+                          const float* clip_factor) {
   PerfScope perf(PERF_CLASS("sgd"), s, 0, 20.0 * (hi - lo));
+  if (clip_factor) {
+    hipLaunchKernelGGL(k_sgd_seg_clip, dim3(nblocks(hi - lo, 4)), dim3(TPB), 0,
+                       s, lo, hi, g_arena, h_arena, seg_off, w_ptrs, lr_mults,
+                       decay_mults, nseg, mom, lr, decay, gscale, clip_factor);
+    ktrace(kSgdSeg, kVarNone, lo, hi, nseg, 1);
+    return;
+  }
   hipLaunchKernelGGL(k_sgd_seg, dim3(nblocks(hi - lo, 4)), dim3(TPB), 0, s,
                      lo, hi, g_arena, h_arena, seg_off, w_ptrs, lr_mults,
                      decay_mults, nseg, mom, lr, decay, gscale);
@@ -1994,6 +2032,32 @@ void sgd_update_segmented(hipStream_t s, long lo, long hi, float* g_arena,
 // so gr == 0 there for L2 and L1 alike, and from a zeroed history every rule
 // leaves them finite: the quotients are 0 / (0 + delta) with delta > 0
 // (AdaGrad, RMSProp, Adam) or 0 * sqrt(delta / delta) (AdaDelta).
+// The loop is a macro for the reason given at SGD_SEG_LOOP.
+#define SOLVER_SEG_LOOP                                                      \
+  constexpr bool kTwo = Rule == kRuleAdaDelta || Rule == kRuleAdam;          \
+  for (long p = lo4 + blockIdx.x * (long)blockDim.x + threadIdx.x; p < hi4;  \
+       p += (long)gridDim.x * blockDim.x) {                                  \
+    const long i = 4 * p;                                                    \
+    const int a = seg_find(seg_off, nseg, i);                                \
+    f4* wp = (f4*)(w_ptrs[a] + (i - seg_off[a]));                            \
+    const float lr = c.lr * lr_mults[a];                                     \
+    const float decay = c.decay * decay_mults[a];                            \
+    const f4 gv = g_arena[p];                                                \
+    f4 wv = *wp, hv = h_arena[p];                                            \
+    f4 h2v = {0.f, 0.f, 0.f, 0.f};                                           \
+    if (kTwo) h2v = h2_arena[p];                                             \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                          \
+      float hj = hv[j], h2j = h2v[j];                                        \
+      wv[j] -= solver_rule_step<Rule, kL1>(gv[j], wv[j], hj, h2j, c, lr,     \
+                                           decay);                           \
+      hv[j] = hj;                                                            \
+      h2v[j] = h2j;                                                          \
+    }                                                                        \
+    *wp = wv;                                                                \
+    h_arena[p] = hv;                                                         \
+    if (kTwo) h2_arena[p] = h2v;                                             \
+    g_arena[p] = f4{0.f, 0.f, 0.f, 0.f};                                     \
+  }
 template <int Rule, bool kL1>
 __global__ void k_solver_seg(long lo4, long hi4, f4* __restrict__ g_arena,
                              f4* __restrict__ h_arena,
@@ -2003,38 +2067,30 @@ __global__ void k_solver_seg(long lo4, long hi4, f4* __restrict__ g_arena,
                              const float* __restrict__ lr_mults,
                              const float* __restrict__ decay_mults, int nseg,
                              SolverCoef c) {
-  constexpr bool kTwo = Rule == kRuleAdaDelta || Rule == kRuleAdam;
-  for (long p = lo4 + blockIdx.x * (long)blockDim.x + threadIdx.x; p < hi4;
-       p += (long)gridDim.x * blockDim.x) {
-    const long i = 4 * p;
-    const int a = seg_find(seg_off, nseg, i);
-    f4* wp = (f4*)(w_ptrs[a] + (i - seg_off[a]));
-    const float lr = c.lr * lr_mults[a];
-    const float decay = c.decay * decay_mults[a];
-    const f4 gv = g_arena[p];
-    f4 wv = *wp, hv = h_arena[p];
-    f4 h2v = {0.f, 0.f, 0.f, 0.f};
-    if (kTwo) h2v = h2_arena[p];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float hj = hv[j], h2j = h2v[j];
-      wv[j] -= solver_rule_step<Rule, kL1>(gv[j], wv[j], hj, h2j, c, lr,
-                                           decay);
-      hv[j] = hj;
-      h2v[j] = h2j;
-    }
-    *wp = wv;
-    h_arena[p] = hv;
-    if (kTwo) h2_arena[p] = h2v;
-    g_arena[p] = f4{0.f, 0.f, 0.f, 0.f};
-  }
+  SOLVER_SEG_LOOP
 }
+// clip_gradients: the clip factor folded into c.gscale once per thread
+template <int Rule, bool kL1>
+__global__ void k_solver_seg_clip(long lo4, long hi4, f4* __restrict__ g_arena,
+                                  f4* __restrict__ h_arena,
+                                  f4* __restrict__ h2_arena,
+                                  const long* __restrict__ seg_off,
+                                  float* const* __restrict__ w_ptrs,
+                                  const float* __restrict__ lr_mults,
+                                  const float* __restrict__ decay_mults,
+                                  int nseg, SolverCoef c,
+                                  const float* __restrict__ factor) {
+  c.gscale *= factor[0];
+  SOLVER_SEG_LOOP
+}
+#undef SOLVER_SEG_LOOP
 void solver_update_segmented(hipStream_t s, int rule, bool l1, long lo,
                              long hi, float* g_arena, float* h_arena,
                              float* h2_arena, const long* seg_off,
                              float* const* w_ptrs, const float* lr_mults,
                              const float* decay_mults, int nseg,
-                             const SolverCoef& coef) {
+                             const SolverCoef& coef,
+                             const float* clip_factor) {
   CHECK_(lo % 4 == 0 && hi % 4 == 0)
       << "solver_update_segmented: range [" << lo << ", " << hi
       << ") is not float4-aligned";
@@ -2048,7 +2104,17 @@ void solver_update_segmented(hipStream_t s, int rule, bool l1, long lo,
   const dim3 grid(nblocks(hi4 - lo4)), block(TPB);
 #define SOLVER_SEG_LAUNCH(R)                                                \
   case R:                                                                   \
-    if (l1)                                                                 \
+    if (clip_factor && l1)                                                  \
+      hipLaunchKernelGGL((k_solver_seg_clip<R, true>), grid, block, 0, s,   \
+                         lo4, hi4, (f4*)g_arena, (f4*)h_arena,              \
+                         (f4*)h2_arena, seg_off, w_ptrs, lr_mults,          \
+                         decay_mults, nseg, coef, clip_factor);             \
+    else if (clip_factor)                                                   \
+      hipLaunchKernelGGL((k_solver_seg_clip<R, false>), grid, block, 0, s,  \
+                         lo4, hi4, (f4*)g_arena, (f4*)h_arena,              \
+                         (f4*)h2_arena, seg_off, w_ptrs, lr_mults,          \
+                         decay_mults, nseg, coef, clip_factor);             \
+    else if (l1)                                                            \
       hipLaunchKernelGGL((k_solver_seg<R, true>), grid, block, 0, s, lo4,   \
                          hi4, (f4*)g_arena, (f4*)h_arena, (f4*)h2_arena,    \
                          seg_off, w_ptrs, lr_mults, decay_mults, nseg,      \
@@ -2068,7 +2134,67 @@ void solver_update_segmented(hipStream_t s, int rule, bool l1, long lo,
     SOLVER_SEG_LAUNCH(kRuleAdam)
   }
 #undef SOLVER_SEG_LAUNCH
-  ktrace(kSolverSeg, rule * 2 + (l1 ? 1 : 0), lo, hi, nseg);
+  ktrace(kSolverSeg, rule * 2 + (l1 ? 1 : 0), lo, hi, nseg,
+         clip_factor ? 1 : 0);
+}
+
+// ------------------------------------------------------ clip_gradients
+// Sum of squares of the arena range [lo4, hi4) (float4 packs), the two-stage
+// deterministic form of the loss sums: each square and every add in double,
+// one double per block into partials[blockIdx.x], no atomics, same grid for
+// the same range.  Arena padding holds zeros, so the padded range is summed
+// whole.  One accumulator per thread: the form with four independent loads
+// and accumulators (what paid off in k_bn_fwd_stats) measured 12% slower
+// here, 5.51 against 6.17 TB/s at 512 MiB (profiles/clip_gradients.txt).
+__global__ void k_grad_sumsq(const f4* __restrict__ g_arena, long lo4,
+                             long hi4, double* __restrict__ partials) {
+  double acc = 0;
+  for (long p = lo4 + blockIdx.x * (long)blockDim.x + threadIdx.x; p < hi4;
+       p += (long)gridDim.x * blockDim.x) {
+    const f4 v = g_arena[p];
+    acc += ((double)v[0] * v[0] + (double)v[1] * v[1]) +
+           ((double)v[2] * v[2] + (double)v[3] * v[3]);
+  }
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+int grad_sumsq_partials(long n) { return pack_grid(n).blocks; }
+int grad_sumsq(hipStream_t s, const float* g_arena, long lo, long hi,
+               double* partials) {
+  CHECK_(lo % 4 == 0 && hi % 4 == 0 && lo < hi)
+      << "grad_sumsq: range [" << lo << ", " << hi
+      << ") is empty or not float4-aligned";
+  PerfScope perf(PERF_CLASS("clip"), s, 0, 4.0 * (hi - lo));
+  const PackGrid g = pack_grid(hi - lo);
+  hipLaunchKernelGGL(k_grad_sumsq, dim3(g.blocks), dim3(TPB), 0, s,
+                     (const f4*)g_arena, lo / 4, hi / 4, partials);
+  ktrace(kGradSumsq, kVarNone, lo, hi, g.blocks, g.passes);
+  return g.blocks;
+}
+
+// one block: the partials of every bucket of the iteration in a fixed order
+// (thread k adds k, k + TPB, ... then the tree), then the clip formula:
+// norm = (float)(sqrt(sumsq) / world), factor = norm > clip ? clip / norm : 1
+// written as that comparison, so a NaN norm does not clip.  out = {norm,
+// factor}; the clipped update kernels read out[1].
+__global__ void k_clip_final(const double* __restrict__ partials, int np,
+                             double world, float clip,
+                             float* __restrict__ out) {
+  double acc = 0;
+  for (int i = threadIdx.x; i < np; i += TPB) acc += partials[i];
+  const double sum = block_sum(acc);
+  if (threadIdx.x == 0) {
+    const float norm = (float)(sqrt(sum) / world);
+    out[0] = norm;
+    out[1] = clip_factor(norm, clip);
+  }
+}
+void clip_finalize(hipStream_t s, const double* partials, int np, int world,
+                   float clip, float* norm_factor) {
+  PerfScope perf(PERF_CLASS("clip"), s, 0, 8.0 * np);
+  hipLaunchKernelGGL(k_clip_final, dim3(1), dim3(TPB), 0, s, partials, np,
+                     (double)world, clip, norm_factor);
+  ktrace(kClipFinal, kVarNone, np);
 }
 
 // Shared params: one owner layer's arena range [lo, hi) gets the diffs of

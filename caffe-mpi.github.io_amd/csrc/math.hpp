@@ -94,6 +94,17 @@ CAMD_HD inline float solver_rule_step(float g, float w, float& h, float& h2,
   }
 }
 
+// clip_gradients (caffe.proto:241-243; the order of SGDSolver::ApplyUpdate,
+// sgd_solver.cpp:102-128: clip, then normalise, regularise, rule).  norm is
+// the global L2 norm of the reduced gradient over world, rounded once to
+// float.  Written as this comparison: a NaN norm does not clip, and
+// clip == 0 zeroes the gradient unless the norm is 0.  The factor multiplies
+// SolverCoef::gscale; one function serves the host (CPU mode) and
+// k_clip_final.
+CAMD_HD inline float clip_factor(float norm, float clip) {
+  return norm > clip ? clip / norm : 1.0f;
+}
+
 // ------------------------------------------------- sigmoid and its losses
 // Per-element formulas of the reference's sigmoid_layer.cpp:10 and
 // sigmoid_cross_entropy_loss_layer.cpp:41-44.  As with the solver rules, one
@@ -260,6 +271,11 @@ void gemm_trace_readers(long* cursor, long* wide64);
 //       learnable blobs> nsrc=<sharing blobs added>
 //   op=contrastive_fwd|contrastive_bwd var=row_thread|row_wave N=<rows>
 //       C=<row width> blocks=<grid>
+//   op=grad_sumsq lo=<lo> hi=<hi> blocks=<grid = partials written>
+//       passes=<grid-stride passes of the busiest thread>
+//   op=clip_final partials=<doubles summed>
+// With clip_gradients set, sgd_seg and solver_seg records end in " clip=1"
+// (the launch read the factor); without it their text is as above.
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
 
@@ -420,7 +436,8 @@ void sgd_update_segmented(hipStream_t s, long lo, long hi, float* g_arena,
                           float* h_arena, const long* seg_off,
                           float* const* w_ptrs, const float* lr_mults,
                           const float* decay_mults, int nseg, float mom,
-                          float lr, float decay, float gscale);
+                          float lr, float decay, float gscale,
+                          const float* clip_factor = nullptr);
 
 // segmented fused update for every rule but plain SGD+L2 (which stays on
 // sgd_update_segmented): same contract — one launch per bucket over the flat
@@ -428,12 +445,32 @@ void sgd_update_segmented(hipStream_t s, long lo, long hi, float* g_arena,
 // arguments — but float4-wide, so lo and hi must be multiples of 4 (arena
 // offsets and padded counts are multiples of 16).  h2_arena is the second
 // history slot (AdaDelta, Adam); nullptr for the one-slot rules.
+//
+// Both take clip_factor, a device pointer to the iteration's clip factor
+// (clip_finalize's norm_factor + 1), or nullptr without clip_gradients.
+// Given, a sibling kernel (k_sgd_seg_clip / k_solver_seg_clip) runs the same
+// per-element body with gscale * *clip_factor, folded once per thread; not
+// given, the launch is the unclipped kernel, argument for argument.
 void solver_update_segmented(hipStream_t s, int rule, bool l1, long lo,
                              long hi, float* g_arena, float* h_arena,
                              float* h2_arena, const long* seg_off,
                              float* const* w_ptrs, const float* lr_mults,
                              const float* decay_mults, int nseg,
-                             const SolverCoef& coef);
+                             const SolverCoef& coef,
+                             const float* clip_factor = nullptr);
+
+// clip_gradients, stage one: partials[b] = Σ g² (each square and the sum in
+// double) of block b's share of the arena range [lo, hi), multiples of 4;
+// float4 packs, grid-stride, fixed order, no atomics.  Returns the number of
+// partials written, grad_sumsq_partials(hi - lo): the pack grid of the
+// range, capped like every flat kernel here.
+int grad_sumsq_partials(long n);
+int grad_sumsq(hipStream_t s, const float* g_arena, long lo, long hi,
+               double* partials);
+// stage two, one block: norm = (float)(sqrt(Σ partials[0..np)) / world) and
+// clip_factor(norm, clip) into norm_factor[0] and [1], on the device
+void clip_finalize(hipStream_t s, const double* partials, int np, int world,
+                   float clip, float* norm_factor);
 
 // Shared params (Net::plan_param_sharing): add the sharers' diffs into one
 // owner layer's padded arena range [lo, hi), multiples of 4.  seg_off: the

@@ -133,6 +133,7 @@ Solver::Solver(const PMsgPtr& sp, int batch_override) : param_(sp) {
   parse_states();
   net_.reset(new Net(net_msg, train_state_, batch_override));
   weight_decay_ = (float)sp->num("weight_decay", 0.0);
+  clip_ = (float)sp->num("clip_gradients", -1.0);  // caffe.proto:243
   const long buckets = sp->inum("reduce_buckets", 6);  // caffe.proto:140
   bucket_budget_ =
       std::max<long>(1, net_->learnable_count() / std::max<long>(1, buckets));
@@ -262,6 +263,9 @@ void Solver::bcast_weights() {
 
 void Reducer::start_iteration() {
   bucket_start_ = bucket_end_ = 0;
+  deferred_.clear();
+  partials_ = 0;
+  sumsq_ = 0.0;
 }
 
 void Reducer::param_ready(int param_id, hipEvent_t done) {
@@ -304,6 +308,15 @@ void Solver::ensure_seg_table() {
                       hipMemcpyHostToDevice));
   HIP_CHECK(hipMemcpy(d_decays_, dcms.data(), n * sizeof(float),
                       hipMemcpyHostToDevice));
+  if (clipping()) {
+    // a bucket's grid is at most the sum of its params' grids (ceil and the
+    // block cap are both subadditive), so this holds any bucketing
+    for (int i = 0; i < n; ++i)
+      clip_partials_cap_ +=
+          gpu::grad_sumsq_partials((long)padded(params[i].count));
+    clip_partials_.reserve(sizeof(double) * clip_partials_cap_);
+    clip_slot_.reserve(2 * sizeof(float));
+  }
 }
 
 void Reducer::flush(hipEvent_t ev) {
@@ -321,25 +334,16 @@ void Reducer::flush(hipEvent_t ev) {
       S.comm_->allreduce(S.net().diff_arena() + first.offset, count,
                          E.comm_stream);
     }
-    // bucket-fused update: one launch over the flat arena range
-    S.ensure_seg_table();
-    // the kernel writes the weights through the table's cached pointers,
-    // behind the blobs' backs: mark each blob's device copy as the newer
-    // one, or a host copy made by an earlier read (param get, snapshot)
-    // would be served again, stale, after this update
-    for (long k = bucket_start_; k < bucket_end_; ++k)
-      params[k].blob->mutable_gpu_data();
-    if (S.rule_ == kRuleSgd && !S.l1_)
-      gpu::sgd_update_segmented(
-          E.comm_stream, first.offset, first.offset + count,
-          S.net().diff_arena(), S.history(), S.d_seg_off_, S.d_w_ptrs_,
-          S.d_lrs_, S.d_decays_, (int)params.size(), S.cur_mom_, S.cur_lr_,
-          S.weight_decay_, S.grad_scale_);
-    else
-      gpu::solver_update_segmented(
-          E.comm_stream, S.rule_, S.l1_, first.offset, first.offset + count,
-          S.net().diff_arena(), S.history(0), S.history(1), S.d_seg_off_,
-          S.d_w_ptrs_, S.d_lrs_, S.d_decays_, (int)params.size(), S.coef());
+    if (S.clipping()) {
+      // the bucket's share of the global norm, behind its all-reduce on the
+      // comm stream; its update waits for the factor (iteration_end)
+      S.ensure_seg_table();
+      const int nb = gpu::grad_sumsq_partials(count);
+      CHECK_LE_(partials_ + nb, S.clip_partials_cap_);
+      partials_ += gpu::grad_sumsq(
+          E.comm_stream, S.net().diff_arena(), first.offset,
+          first.offset + count, (double*)S.clip_partials_.p + partials_);
+    }
   } else {
     if (S.comm_ && S.comm_->world() > 1) {
       // CPU buckets: gather the param diffs into one flat range is
@@ -348,7 +352,58 @@ void Reducer::flush(hipEvent_t ev) {
         S.comm_->allreduce(params[k].blob->mutable_cpu_diff(),
                            params[k].count, nullptr);
     }
-    for (long k = bucket_start_; k < bucket_end_; ++k) {
+    if (S.clipping())
+      // each square and each add in double, per param in learnable order
+      for (long k = bucket_start_; k < bucket_end_; ++k) {
+        const float* g = params[k].blob->cpu_diff();
+        double sum = 0.0;
+        for (long i = 0; i < params[k].count; ++i)
+          sum += (double)g[i] * (double)g[i];
+        sumsq_ += sum;
+      }
+  }
+  if (S.clipping())
+    deferred_.emplace_back(bucket_start_, bucket_end_);
+  else
+    update(bucket_start_, bucket_end_);
+  bucket_start_ = bucket_end_;
+}
+
+// One bucket's update: params [begin, end).  Without clip_gradients it runs
+// straight from flush; with it, from iteration_end once the factor is known
+// (on the device in GPU mode, in coef() in CPU mode).
+void Reducer::update(long begin, long end) {
+  Solver& S = *solver_;
+  Engine& E = Engine::get();
+  auto& params = S.net().learnable_params();
+  const auto& first = params[begin];
+  const auto& last = params[end - 1];
+  const long count = last.offset + (long)padded(last.count) - first.offset;
+  if (E.mode == Mode::GPU) {
+    const float* factor =
+        S.clipping() ? (const float*)S.clip_slot_.p + 1 : nullptr;
+    // bucket-fused update: one launch over the flat arena range
+    S.ensure_seg_table();
+    // the kernel writes the weights through the table's cached pointers,
+    // behind the blobs' backs: mark each blob's device copy as the newer
+    // one, or a host copy made by an earlier read (param get, snapshot)
+    // would be served again, stale, after this update
+    for (long k = begin; k < end; ++k)
+      params[k].blob->mutable_gpu_data();
+    if (S.rule_ == kRuleSgd && !S.l1_)
+      gpu::sgd_update_segmented(
+          E.comm_stream, first.offset, first.offset + count,
+          S.net().diff_arena(), S.history(), S.d_seg_off_, S.d_w_ptrs_,
+          S.d_lrs_, S.d_decays_, (int)params.size(), S.cur_mom_, S.cur_lr_,
+          S.weight_decay_, S.grad_scale_, factor);
+    else
+      gpu::solver_update_segmented(
+          E.comm_stream, S.rule_, S.l1_, first.offset, first.offset + count,
+          S.net().diff_arena(), S.history(0), S.history(1), S.d_seg_off_,
+          S.d_w_ptrs_, S.d_lrs_, S.d_decays_, (int)params.size(), S.coef(),
+          factor);
+  } else {
+    for (long k = begin; k < end; ++k) {
       const auto& p = params[k];
       float* g = p.blob->mutable_cpu_diff();
       float* w = p.blob->mutable_cpu_data();
@@ -358,12 +413,28 @@ void Reducer::flush(hipEvent_t ev) {
                       S.upd_lr_ * p.lr_mult, S.weight_decay_ * p.decay_mult);
     }
   }
-  bucket_start_ = bucket_end_;
 }
 
 void Reducer::iteration_end(hipEvent_t backward_done) {
   flush(backward_done);
   Engine& E = Engine::get();
+  Solver& S = *solver_;
+  if (S.clipping()) {
+    const int world = S.comm_ && S.comm_->world() > 1 ? S.comm_->world() : 1;
+    if (E.mode == Mode::GPU) {
+      // (a net without learnable params has no bucket, no slot, no launch)
+      if (partials_ > 0)
+        gpu::clip_finalize(E.comm_stream, (const double*)S.clip_partials_.p,
+                           partials_, world, S.clip_,
+                           (float*)S.clip_slot_.p);
+    } else {
+      S.clip_norm_ = (float)(std::sqrt(sumsq_) / world);
+      S.clip_factor_ = clip_factor(S.clip_norm_, S.clip_);
+    }
+    for (const auto& b : deferred_) update(b.first, b.second);
+    deferred_.clear();
+    ++S.clip_iters_;
+  }
   if (E.mode == Mode::GPU) {
     if (!comm_done_ev_)
       HIP_CHECK(
@@ -456,6 +527,7 @@ void Solver::Step(int iters) {
       const float l = net_->loss();
       fprintf(stderr, "[caffe_amd] Iteration %ld, loss = %g, lr = %g\n",
               iter_, l, cur_lr_);
+      if (clipping()) report_clipping();
     }
   }
   if (timed) {
@@ -479,6 +551,33 @@ void Solver::copy_history(int slot, int param_index, float* out, long count) {
   CHECK_LE_(count, p.count);
   Engine::get().sync();  // the updates run on comm_stream
   history_[slot].read(p.offset, count, out);
+}
+
+void Solver::grad_norm(float* norm, float* factor) {
+  CHECK_(clipping()) << "grad_norm: this solver has no clip_gradients "
+                        "(the norm is computed only for clipping)";
+  CHECK_(clip_iters_ > 0) << "grad_norm: no iteration has finished yet";
+  Engine& E = Engine::get();
+  float nf[2] = {clip_norm_, clip_factor_};
+  if (E.mode == Mode::GPU && clip_slot_.p) {
+    // the finalize and the updates run on the comm stream
+    HIP_CHECK(hipStreamSynchronize(E.comm_stream));
+    HIP_CHECK(hipMemcpy(nf, clip_slot_.p, sizeof(nf), hipMemcpyDeviceToHost));
+  }
+  *norm = nf[0];
+  *factor = nf[1];
+}
+
+// the reference's line (sgd_solver.cpp:122-125), on display iterations only:
+// Step reads the loss back there anyway
+void Solver::report_clipping() {
+  float norm = 0.f, factor = 1.f;
+  grad_norm(&norm, &factor);
+  if (norm > clip_)
+    fprintf(stderr,
+            "[caffe_amd] Gradient clipping: scaling down gradients (L2 norm "
+            "%g > %g) by scale factor %g\n",
+            norm, clip_, factor);
 }
 
 std::shared_ptr<Solver> create_solver_from_file(const std::string& path,

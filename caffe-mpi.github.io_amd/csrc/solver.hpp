@@ -11,6 +11,14 @@
 // hipEvent recorded after the producing layer's backward, so the collective
 // overlaps the rest of backward exactly as the reference's thread did, with
 // no host synchronization in the loop.
+//
+// clip_gradients (caffe.proto:241-243, SGDSolver::ClipGradients
+// sgd_solver.cpp:111-128) needs the norm of the whole reduced gradient, known
+// only after the last bucket: with the field set, a bucket's flush still
+// runs its all-reduce at once and follows it with the bucket's sum of
+// squares instead of its update; iteration_end launches the finalize
+// ({norm, factor} into a device slot) and then the deferred updates, which
+// read the factor from device memory.  Still no host wait in the loop.
 #pragma once
 
 #include "net.hpp"
@@ -81,10 +89,18 @@ class Reducer : public ReduceHook {
 
  private:
   void flush(hipEvent_t ev);
+  // the update of params [begin, end), one bucket
+  void update(long begin, long end);
   Solver* solver_;
   long bucket_start_ = 0;   // param index where current bucket starts
   long bucket_end_ = 0;     // one past last ready param
   hipEvent_t comm_done_ev_ = nullptr;
+  // clip_gradients: the buckets whose update waits for the factor, in
+  // arrival order, and the iteration's sum of squares so far — partials
+  // written to the solver's device buffer, or the host sum in CPU mode
+  std::vector<std::pair<long, long>> deferred_;
+  int partials_ = 0;
+  double sumsq_ = 0.0;
 };
 
 class Solver {
@@ -123,6 +139,12 @@ class Solver {
   // order, as Net::learnable_params) to out, from the device or the host
   void copy_history(int slot, int param_index, float* out, long count);
   float last_loss() { return net_->loss(); }
+  // SolverParameter.clip_gradients (caffe.proto:241-243); < 0 = off
+  float clip_gradients() const { return clip_; }
+  bool clipping() const { return clip_ >= 0.f; }
+  // the last finished iteration's gradient norm and clip factor; syncs the
+  // comm stream.  An error with clipping off or before the first step.
+  void grad_norm(float* norm, float* factor);
   const PMsgPtr& param() const { return param_; }
 
   void set_action_request(ActionRequestFn fn) { action_fn_ = fn; }
@@ -146,12 +168,17 @@ class Solver {
   // per-iteration cached coefficients for the fused update
   float cur_lr_ = 0.f, cur_mom_ = 0.f, weight_decay_ = 0.f;
   float grad_scale_ = 1.f;
+  // clip_gradients, CPU mode: the iteration's factor, folded into coef()'s
+  // gscale (1 when off or not firing, which leaves grad_scale_'s bits); in
+  // GPU mode the factor stays on the device and this stays 1
+  float clip_factor_ = 1.f;
+  float clip_norm_ = 0.f;
   // cur_lr_ for the update: Adam folds this iteration's bias correction in
   float upd_lr_ = 0.f;
   long bucket_budget_ = 0;  // elements per bucket
   SolverCoef coef() const {
-    return SolverCoef{cur_mom_, upd_lr_, weight_decay_, grad_scale_, aux_,
-                      delta_};
+    return SolverCoef{cur_mom_, upd_lr_, weight_decay_,
+                      grad_scale_ * clip_factor_, aux_, delta_};
   }
 
  private:
@@ -188,6 +215,14 @@ class Solver {
   float* d_lrs_ = nullptr;    // per-param lr MULTIPLIERS (uploaded once)
   float* d_decays_ = nullptr; // per-param decay multipliers
   void ensure_seg_table();
+  // clip_gradients (GPU mode), allocated once with the segment table: one
+  // double per block of every bucket's sum-of-squares launch, and the
+  // {norm, factor} slot the finalize writes and the updates read
+  float clip_ = -1.f;
+  DeviceBuf clip_partials_, clip_slot_;
+  int clip_partials_cap_ = 0;
+  long clip_iters_ = 0;  // iterations that went through the clip path
+  void report_clipping();
   // iter_size accumulation buffer (diff-arena layout; only allocated when
   // iter_size > 1 — layer backwards overwrite their param diffs, so cross-
   // pass accumulation happens here instead of in every wgrad kernel)

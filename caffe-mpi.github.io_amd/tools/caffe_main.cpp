@@ -221,6 +221,8 @@ static int run_train_rank(std::map<std::string, std::string> flags, int dev,
   }
   Solver solver(sp, batch_override);
   if (grank == 0) fprintf(stderr, "Solver type: %s\n", solver.type());
+  if (grank == 0 && solver.clipping())
+    fprintf(stderr, "Gradient clipping: %g\n", solver.clip_gradients());
   // the reference's Net::AppendParam line, once per sharing param blob
   for (auto& s : solver.net().param_sharing())
     if (grank == 0)

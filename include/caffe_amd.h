@@ -105,6 +105,15 @@ int caffe_solver_history_slots(caffe_solver_t s);
  * count <= the param's element count — syncs */
 int caffe_solver_history(caffe_solver_t s, int slot, int param_index,
                          float* out, long count);
+/* SolverParameter.clip_gradients as parsed (caffe.proto:241-243; the bound
+ * of SGDSolver::ClipGradients, sgd_solver.cpp:111-128); negative = off */
+float caffe_solver_clip_gradients(caffe_solver_t s);
+/* the last finished iteration's global L2 gradient norm (over all learnable
+ * params, after the all-reduce, over world) and the factor it was scaled by:
+ * l2norm_diff and scale_factor of SGDSolver::ClipGradients
+ * (sgd_solver.cpp:111-128), taken once per iteration — syncs the comm
+ * stream.  -1 with clip_gradients off or before the first step. */
+int caffe_solver_grad_norm(caffe_solver_t s, float* norm, float* factor);
 /* Net weight interop (net.cpp:1055-1248) */
 int caffe_net_save_weights(caffe_net_t n, const char* path);
 int caffe_net_load_weights(caffe_net_t n, const char* path);

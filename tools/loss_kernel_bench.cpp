@@ -1,13 +1,15 @@
 // loss_kernel_bench.cpp — times the Sigmoid / SigmoidCrossEntropyLoss /
 // EuclideanLoss kernels against the kernels of the same traffic class that
 // the engine already had: ReLU forward / backward (same bytes per element)
-// and the float4 BatchNorm statistics kernel (the existing block reduce).
+// and the float4 BatchNorm statistics kernel (the existing block reduce);
+// beside them the clip_gradients sum of squares.
 // One process, the variants alternated round by round, one large element
 // count (512 MiB per tensor, beyond the Infinity Cache).
 //
 //   make -C caffe-mpi.github.io_amd loss-kernel-bench
 //   tools/loss_kernel_bench [rounds]     # table of profiles/sigmoid_loss_kernels.txt
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -67,6 +69,10 @@ int main(int argc, char** argv) {
       {"k_euclid_fwd", 2 * fb,
        [&](hipStream_t st) { gpu::euclid_fwd(st, a, b, n, N, partials, loss); },
        {}},
+      // clip_gradients: the sum of squares over one stream
+      // (profiles/clip_gradients.txt); one partial per block, no final sum
+      {"k_grad_sumsq", fb,
+       [&](hipStream_t st) { gpu::grad_sumsq(st, a, 0, n, partials); }, {}},
       {"k_sigmoid_ce_bwd", 3 * fb,
        [&](hipStream_t st) { gpu::sigmoid_ce_bwd(st, a, b, n, 1.f / N, c); },
        {}},
@@ -91,6 +97,15 @@ int main(int argc, char** argv) {
     }
   float h_loss = 0;
   HIP_CHECK(hipMemcpy(&h_loss, loss, sizeof(float), hipMemcpyDeviceToHost));
+  // the norm the clip path would report for tensor a, against its expectation
+  float nf[2];
+  const int np = gpu::grad_sumsq(s, a, 0, n, partials);
+  gpu::clip_finalize(s, partials, np, 1, 1.f, loss);
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipMemcpy(nf, loss, sizeof(nf), hipMemcpyDeviceToHost));
+  printf("# grad_sumsq norm %.9g, factor at clip 1 %.9g (uniform [-3, 3): "
+         "sqrt(3 n) = %.9g)\n",
+         nf[0], nf[1], std::sqrt(3.0 * n));
   printf("# n = %ld floats per tensor (%.0f MiB), %d alternated rounds, one "
          "process; last loss written %g\n",
          n, fb / 1048576.0, rounds, h_loss);
