@@ -92,6 +92,7 @@ _lib.caffe_net_diff_sharing.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_net_param_sharing.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_fastdiv_selftest.argtypes = [ctypes.c_uint, ctypes.c_uint]
 _lib.caffe_fastdiv_selftest.restype = ctypes.c_long
+_lib.caffe_device_live_bytes.restype = ctypes.c_size_t
 
 _f32p = ctypes.POINTER(ctypes.c_float)
 _lib.caffe_net_blob_get.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int,
@@ -171,6 +172,12 @@ def set_perf_timing(enable):
 
 def device_synchronize():
     _ck(_lib.caffe_device_synchronize())
+
+
+def device_live_bytes():
+    """Device bytes the engine's allocator has handed out and not got back
+    (blocks it caches for reuse are not counted)."""
+    return _lib.caffe_device_live_bytes()
 
 
 def perf_snapshot():

@@ -11,8 +11,10 @@ using namespace camd;
 
 namespace {
 thread_local std::string g_err;
-std::vector<std::shared_ptr<Solver>> g_solvers;
-std::vector<std::shared_ptr<Net>> g_nets;
+// the live handles; never deleted, like the Engine (Engine::get): a handle
+// is freed by caffe_solver_free / caffe_net_free or not at all
+auto* const g_solvers = new std::map<void*, std::shared_ptr<Solver>>;
+auto* const g_nets = new std::map<void*, std::shared_ptr<Net>>;
 
 #define API_TRY try {
 #define API_CATCH                      \
@@ -125,7 +127,7 @@ int caffe_set_perf_timing(int enable) {
 caffe_solver_t caffe_solver_create(const char* path, int batch_override) {
   API_TRY
   auto s = create_solver_from_file(path, batch_override);
-  g_solvers.push_back(s);
+  (*g_solvers)[s.get()] = s;
   return (caffe_solver_t)s.get();
   API_CATCH_NULL
 }
@@ -134,18 +136,12 @@ caffe_solver_t caffe_solver_create_from_text(const char* text,
                                              int batch_override) {
   API_TRY
   auto s = std::make_shared<Solver>(parse_prototxt(text), batch_override);
-  g_solvers.push_back(s);
+  (*g_solvers)[s.get()] = s;
   return (caffe_solver_t)s.get();
   API_CATCH_NULL
 }
 
-void caffe_solver_free(caffe_solver_t s) {
-  for (auto it = g_solvers.begin(); it != g_solvers.end(); ++it)
-    if (it->get() == s) {
-      g_solvers.erase(it);
-      return;
-    }
-}
+void caffe_solver_free(caffe_solver_t s) { g_solvers->erase(s); }
 
 int caffe_solver_step(caffe_solver_t s, int iters) {
   API_TRY
@@ -303,7 +299,7 @@ caffe_net_t caffe_net_create(const char* path, int phase,
   auto n = std::make_shared<Net>(parse_prototxt_file(path),
                                  phase ? Phase::TEST : Phase::TRAIN,
                                  batch_override);
-  g_nets.push_back(n);
+  (*g_nets)[n.get()] = n;
   return (caffe_net_t)n.get();
   API_CATCH_NULL
 }
@@ -323,18 +319,12 @@ caffe_net_t caffe_net_create_state(const char* path, int phase, int level,
   }
   auto n = std::make_shared<Net>(parse_prototxt_file(path), st,
                                  batch_override);
-  g_nets.push_back(n);
+  (*g_nets)[n.get()] = n;
   return (caffe_net_t)n.get();
   API_CATCH_NULL
 }
 
-void caffe_net_free(caffe_net_t n) {
-  for (auto it = g_nets.begin(); it != g_nets.end(); ++it)
-    if (it->get() == n) {
-      g_nets.erase(it);
-      return;
-    }
-}
+void caffe_net_free(caffe_net_t n) { g_nets->erase(n); }
 
 int caffe_net_forward(caffe_net_t n) {
   API_TRY
@@ -527,6 +517,10 @@ int caffe_device_synchronize(void) {
   Engine::get().drain_events();
   return 0;
   API_CATCH
+}
+
+size_t caffe_device_live_bytes(void) {
+  return Engine::get().dalloc.live_bytes();
 }
 
 int caffe_perf_snapshot(char* names, int name_cap, long* launches,

@@ -3,8 +3,8 @@
 namespace camd {
 
 Engine& Engine::get() {
-  static Engine e;
-  return e;
+  static Engine* const e = new Engine;
+  return *e;
 }
 
 namespace {
@@ -56,6 +56,7 @@ void* DeviceAllocator::alloc(size_t bytes) {
   // partial chunks (values are dropped or masked, but the BYTES must be
   // mapped) — without slack the last row of a tensor can touch the next
   // page (observed as a GPU memory-access fault under the glds kernel)
+  live_ += bytes;
   bytes += 64;
   {
     std::lock_guard<std::mutex> g(mu_);
@@ -76,6 +77,7 @@ void* DeviceAllocator::alloc(size_t bytes) {
 }
 
 void DeviceAllocator::release(void* p, size_t bytes) {
+  live_ -= bytes;
   bytes += 64;  // must mirror alloc()'s safety-tail key
   std::lock_guard<std::mutex> g(mu_);
   free_.emplace(bytes, p);
@@ -93,6 +95,11 @@ void* DeviceBuf::reserve(size_t want) {
     p = Engine::get().dalloc.alloc(want);
     bytes = want;
   }
+  return p;
+}
+void* DeviceBuf::upload(const void* src, size_t n) {
+  reserve(n);
+  if (n) HIP_CHECK(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
   return p;
 }
 DeviceBuf::~DeviceBuf() {

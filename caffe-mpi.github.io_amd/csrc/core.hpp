@@ -118,27 +118,56 @@ class DeviceAllocator {
  public:
   void* alloc(size_t bytes);
   void release(void* p, size_t bytes);
-  void free_all();
-  ~DeviceAllocator() { free_all(); }
+  void free_all();  // the out-of-memory retry: hipFree every cached block
+  // requested bytes handed out and not yet released; cached blocks are not
+  size_t live_bytes() const { return live_; }
 
  private:
   std::multimap<size_t, void*> free_;
   std::mutex mu_;
+  std::atomic<size_t> live_{0};
 };
 
 // A device buffer that one object owns and keeps across calls (a conv
-// layer's cached col buffer, the data feed's upload targets).  It comes
-// from Engine::dalloc, so it has the allocator's +64 B tail; it grows only
-// when asked for more (the old contents are dropped), has no host mirror
-// and is never zero-filled; the owner's destructor returns it to dalloc.
+// layer's cached col buffer, the net's diff arena, every device table).  It
+// comes from Engine::dalloc, so it has the allocator's +64 B tail; it grows
+// only when asked for more (the old contents are dropped), has no host
+// mirror and is never zero-filled; its destructor returns it to dalloc.
+// It never waits: an object whose device memory kernels on either stream may
+// still touch (Net, Solver) calls Engine::sync() once at the top of its
+// destructor, and its members then release themselves.
 struct DeviceBuf {
   void* p = nullptr;
   size_t bytes = 0;
   void* reserve(size_t want);  // p, grown first when want > bytes
+  // reserve + a blocking copy from (pageable) host memory
+  void* upload(const void* src, size_t bytes);
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
   DeviceBuf() = default;
   DeviceBuf(const DeviceBuf&) = delete;
   DeviceBuf& operator=(const DeviceBuf&) = delete;
   ~DeviceBuf();
+};
+
+// A hipEvent_t (timing disabled) that one object owns; move-only.  Default-
+// constructed it holds no event (CPU mode, vector elements before create()).
+class GpuEvent {
+ public:
+  GpuEvent() = default;
+  GpuEvent(GpuEvent&& o) noexcept : ev_(o.ev_) { o.ev_ = nullptr; }
+  ~GpuEvent() {
+    if (ev_) (void)hipEventDestroy(ev_);
+  }
+  void create() {
+    if (!ev_) HIP_CHECK(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
+  }
+  hipEvent_t get() const { return ev_; }
+
+ private:
+  hipEvent_t ev_ = nullptr;
 };
 
 struct PerfClass {
@@ -161,6 +190,9 @@ struct PerfClass {
 // common.hpp:334-345 per-thread streams; here one process == one device).
 class Engine {
  public:
+  // A heap object that is never deleted, like the C ABI's handle lists: no
+  // engine destructor runs at process exit (the driver reclaims the device),
+  // so every explicit free of a net or solver finds the allocator alive.
   static Engine& get();
 
   Mode mode = Mode::CPU;

@@ -543,15 +543,12 @@ void Net::apply_diff_sharing() {
 void Net::setup_arena() {
   if (params_.empty()) return;
   Engine& E = Engine::get();
-  diff_arena_ =
-      (float*)E.dalloc.alloc(sizeof(float) * (size_t)arena_count_);
-  HIP_CHECK(hipMemsetAsync(diff_arena_, 0,
-                           sizeof(float) * (size_t)arena_count_, E.stream));
+  const size_t bytes = sizeof(float) * (size_t)arena_count_;
+  HIP_CHECK(hipMemsetAsync(diff_arena_.reserve(bytes), 0, bytes, E.stream));
   for (auto& p : params_)
-    p.blob->diff_mem().set_gpu_view(diff_arena_ + p.offset);
-  layer_events_.resize(layers_.size(), nullptr);
-  for (auto& ev : layer_events_)
-    HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    p.blob->diff_mem().set_gpu_view(diff_arena() + p.offset);
+  layer_events_.resize(layers_.size());
+  for (auto& ev : layer_events_) ev.create();
 }
 
 // What Backward adds after each owner layer: the sharers of the layer's
@@ -593,29 +590,16 @@ void Net::setup_shared_sums() {
     ss.nseg = (int)seg_off.size() - ss.seg_start;
   }
   src_begin.push_back((int)srcs.size());  // the one closing bound
-  sum_nseg_ = seg_off.size();
-  sum_nsrc_ = srcs.size();
-  Engine& E = Engine::get();
-  d_sum_seg_off_ = (long*)E.dalloc.alloc(seg_off.size() * sizeof(long));
-  d_sum_src_begin_ = (int*)E.dalloc.alloc(src_begin.size() * sizeof(int));
-  d_sum_srcs_ = (const float**)E.dalloc.alloc(srcs.size() * sizeof(float*));
-  HIP_CHECK(hipMemcpy(d_sum_seg_off_, seg_off.data(),
-                      seg_off.size() * sizeof(long), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_sum_src_begin_, src_begin.data(),
-                      src_begin.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_sum_srcs_, srcs.data(), srcs.size() * sizeof(float*),
-                      hipMemcpyHostToDevice));
+  d_sum_seg_off_.upload(seg_off.data(), seg_off.size() * sizeof(long));
+  d_sum_src_begin_.upload(src_begin.data(), src_begin.size() * sizeof(int));
+  d_sum_srcs_.upload(srcs.data(), srcs.size() * sizeof(float*));
 }
 
-// The sum tables go back to the caching allocator, which may hand them to
-// the next net: wait for the last launch that reads them first.
+// The arena and the sum tables go back to the caching allocator, which may
+// hand them to the next owner: wait first, on both streams (the reducer
+// reads the arena on the comm stream).
 Net::~Net() {
-  if (!d_sum_seg_off_) return;
-  Engine& E = Engine::get();
-  (void)hipStreamSynchronize(E.stream);
-  E.dalloc.release(d_sum_seg_off_, sum_nseg_ * sizeof(long));
-  E.dalloc.release(d_sum_src_begin_, (sum_nseg_ + 1) * sizeof(int));
-  E.dalloc.release(d_sum_srcs_, sum_nsrc_ * sizeof(float*));
+  if (diff_arena_.p || d_sum_seg_off_.p) Engine::get().sync();
 }
 
 // Layer backwards overwrite their param diffs, so a sharer writes its own
@@ -627,10 +611,10 @@ void Net::sum_shared_diffs(int i) {
   const SharedSum& ss = it->second;
   Engine& E = Engine::get();
   if (E.mode == Mode::GPU) {
-    gpu::shared_diff_sum(E.stream, ss.lo, ss.hi, diff_arena_,
-                         d_sum_seg_off_ + ss.seg_start, ss.nseg,
-                         d_sum_src_begin_ + ss.seg_start, d_sum_srcs_,
-                         (int)ss.srcs.size());
+    gpu::shared_diff_sum(E.stream, ss.lo, ss.hi, diff_arena(),
+                         d_sum_seg_off_.as<long>() + ss.seg_start, ss.nseg,
+                         d_sum_src_begin_.as<int>() + ss.seg_start,
+                         d_sum_srcs_.as<const float*>(), (int)ss.srcs.size());
   } else {
     for (auto& src : ss.srcs)
       cpu::axpy(src.owner->count(), 1.f, src.sharer->cpu_diff(),
@@ -669,7 +653,7 @@ void Net::Backward(ReduceHook* hook) {
       if (pidx > start) {
         hipEvent_t ev = nullptr;
         if (E.mode == Mode::GPU) {
-          ev = layer_events_[i];
+          ev = layer_events_[i].get();
           HIP_CHECK(hipEventRecord(ev, E.stream));
           last_ev = ev;
         }
@@ -680,7 +664,7 @@ void Net::Backward(ReduceHook* hook) {
   if (hook) {
     hipEvent_t ev = last_ev;
     if (E.mode == Mode::GPU && !ev) {
-      ev = layer_events_[0];
+      ev = layer_events_[0].get();
       HIP_CHECK(hipEventRecord(ev, E.stream));
     }
     hook->iteration_end(ev);

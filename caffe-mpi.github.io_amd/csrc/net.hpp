@@ -89,8 +89,7 @@ class Net {
     });
     return idx;
   }
-  float* diff_arena() { return diff_arena_; }
-  float* data_arena() { return nullptr; }  // weights stay per-blob this round
+  float* diff_arena() { return diff_arena_.as<float>(); }
 
   const std::vector<std::shared_ptr<Layer>>& layers() const {
     return layers_;
@@ -240,18 +239,19 @@ class Net {
     int seg_start = 0, nseg = 0;  // into d_sum_seg_off_ / d_sum_src_begin_
   };
   std::map<int, SharedSum> shared_sums_;  // by owner layer index
-  // Device tables, returned to the allocator in ~Net.  The segments of all
-  // owner layers stand one after another, in owner-layer order, and so do
-  // their sources: segment k's sources are srcs[src_begin[k] ..
-  // src_begin[k + 1]), with ONE closing bound after the last segment of the
-  // last layer (a layer's slice starts at its seg_start in both tables).
-  long* d_sum_seg_off_ = nullptr;       // arena offset of every segment
-  int* d_sum_src_begin_ = nullptr;      // segments + 1 source bounds
-  const float** d_sum_srcs_ = nullptr;  // the sharers' diff pointers
-  size_t sum_nseg_ = 0, sum_nsrc_ = 0;  // entries: segments, sources
+  // Device tables.  The segments of all owner layers stand one after
+  // another, in owner-layer order, and so do their sources: segment k's
+  // sources are srcs[src_begin[k] .. src_begin[k + 1]), with ONE closing
+  // bound after the last segment of the last layer (a layer's slice starts
+  // at its seg_start in both tables).
+  DeviceBuf d_sum_seg_off_;    // long: arena offset of every segment
+  DeviceBuf d_sum_src_begin_;  // int: segments + 1 source bounds
+  DeviceBuf d_sum_srcs_;       // const float*: the sharers' diff pointers
   long arena_count_ = 0;
-  float* diff_arena_ = nullptr;
-  std::vector<hipEvent_t> layer_events_;
+  // declared after layers_: the arena goes before the blobs whose diffs are
+  // non-owning views of it
+  DeviceBuf diff_arena_;
+  std::vector<GpuEvent> layer_events_;
 };
 
 }  // namespace camd

@@ -86,16 +86,15 @@ int rccl_selftest() {
   NCCL_CHECK(ncclGetUniqueId(&id));
   RcclComm comm(0, 1, &id);
   const long n = 4096;
-  float* buf = (float*)E.dalloc.alloc(n * sizeof(float));
   std::vector<float> host(n);
   for (long i = 0; i < n; ++i) host[i] = (float)(i % 97) * 0.5f;
-  HIP_CHECK(hipMemcpy(buf, host.data(), n * 4, hipMemcpyHostToDevice));
+  DeviceBuf dev;
+  float* buf = (float*)dev.upload(host.data(), n * sizeof(float));
   comm.allreduce(buf, n, E.stream);
   comm.bcast(buf, n, 0, E.stream);
   HIP_CHECK(hipStreamSynchronize(E.stream));
   std::vector<float> out(n);
   HIP_CHECK(hipMemcpy(out.data(), buf, n * 4, hipMemcpyDeviceToHost));
-  E.dalloc.release(buf, n * sizeof(float));
   for (long i = 0; i < n; ++i)
     CHECK_EQ_(out[i], host[i]) << "rccl world-1 allreduce mismatch at " << i;
   return 0;

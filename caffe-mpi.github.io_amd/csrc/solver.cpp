@@ -139,43 +139,70 @@ Solver::Solver(const PMsgPtr& sp, int batch_override) : param_(sp) {
       std::max<long>(1, net_->learnable_count() / std::max<long>(1, buckets));
   for (int slot = 0; slot < history_slots(); ++slot)
     history_[slot].alloc(net_->learnable_count());
+  if (E.mode == Mode::GPU) tables_.build(*net_, clipping());
 }
 
-void StateBuf::alloc(long count) {
-  Engine& E = Engine::get();
-  count_ = count;
-  if (count == 0) return;
-  if (E.mode == Mode::GPU) {
-    dev_ = (float*)E.dalloc.alloc(sizeof(float) * count);
-    zero();
-  } else {
-    host_.assign(count, 0.f);
+Solver::~Solver() { Engine::get().sync(); }
+
+// Safe at construction: a param blob's device pointer is fixed once allocated
+// (no param blob is reshaped after the net build, sharers were re-pointed
+// during it, and every later write of the weights goes through the host copy
+// into the same device memory).  This uploads the weights.
+void Solver::UpdateTables::build(Net& net, bool clipping) {
+  auto& params = net.learnable_params();
+  nseg = (int)params.size();
+  std::vector<long> offs(nseg);
+  std::vector<float*> wps(nseg);
+  std::vector<float> lrms(nseg), dcms(nseg);
+  for (int i = 0; i < nseg; ++i) {
+    offs[i] = params[i].offset;
+    wps[i] = params[i].blob->mutable_gpu_data();
+    lrms[i] = params[i].lr_mult;
+    dcms[i] = params[i].decay_mult;
+  }
+  seg_off.upload(offs.data(), nseg * sizeof(long));
+  w_ptrs.upload(wps.data(), nseg * sizeof(float*));
+  lrs.upload(lrms.data(), nseg * sizeof(float));
+  decays.upload(dcms.data(), nseg * sizeof(float));
+  if (clipping && nseg > 0) {  // no params: no finalize ever writes a slot
+    // a bucket's grid is at most the sum of its params' grids (ceil and the
+    // block cap are both subadditive), so this holds any bucketing
+    for (int i = 0; i < nseg; ++i)
+      clip_partials_cap +=
+          gpu::grad_sumsq_partials((long)padded(params[i].count));
+    clip_partials.reserve(sizeof(double) * clip_partials_cap);
+    clip_slot.reserve(2 * sizeof(float));
   }
 }
 
-StateBuf::~StateBuf() {
-  if (dev_) Engine::get().dalloc.release(dev_, sizeof(float) * count_);
+void StateBuf::alloc(long count) {
+  count_ = count;
+  if (Engine::get().mode == Mode::GPU)
+    dev_.reserve(sizeof(float) * count);
+  else
+    host_.resize(count);
+  zero();
 }
 
 void StateBuf::zero() {
-  if (dev_)
-    HIP_CHECK(hipMemsetAsync(dev_, 0, sizeof(float) * count_,
+  if (dev_.p)
+    HIP_CHECK(hipMemsetAsync(dev_.p, 0, sizeof(float) * count_,
                              Engine::get().stream));
   else
     std::fill(host_.begin(), host_.end(), 0.f);
 }
 
 void StateBuf::read(long offset, long count, float* out) {
-  if (dev_)
-    HIP_CHECK(hipMemcpy(out, dev_ + offset, sizeof(float) * count,
+  if (dev_.p)
+    HIP_CHECK(hipMemcpy(out, dev_.as<float>() + offset, sizeof(float) * count,
                         hipMemcpyDeviceToHost));
   else
     memcpy(out, host_.data() + offset, sizeof(float) * count);
 }
 
 void StateBuf::write(long offset, const float* in, long count) {
-  if (dev_)
-    HIP_CHECK(hipMemcpy(dev_ + offset, in, sizeof(float) * count,
+  if (dev_.p)
+    HIP_CHECK(hipMemcpy(dev_.as<float>() + offset, in, sizeof(float) * count,
                         hipMemcpyHostToDevice));
   else
     memcpy(host_.data() + offset, in, sizeof(float) * count);
@@ -268,55 +295,17 @@ void Reducer::start_iteration() {
   sumsq_ = 0.0;
 }
 
-void Reducer::param_ready(int param_id, hipEvent_t done) {
+std::pair<long, long> Reducer::range(long begin, long end) const {
   auto& params = solver_->net().learnable_params();
-  CHECK_EQ_((long)param_id, bucket_end_) << "params must arrive in order";
-  bucket_end_ = param_id + 1;
-  const auto& first = params[bucket_start_];
-  const auto& last = params[bucket_end_ - 1];
-  const long span = last.offset + (long)padded(last.count) - first.offset;
-  if (span >= solver_->bucket_budget_) flush(done);
+  const auto& last = params[end - 1];
+  return {params[begin].offset, last.offset + (long)padded(last.count)};
 }
 
-void Solver::ensure_seg_table() {
-  // the table holds per-param lr/decay MULTIPLIERS (immutable after net
-  // build) — per-iteration lr/decay are kernel arguments, so the table is
-  // uploaded exactly once, synchronously (no pageable-async lifetime
-  // hazard, no H2D copies in the iteration loop)
-  if (d_seg_off_) return;
-  Engine& E = Engine::get();
-  auto& params = net_->learnable_params();
-  const int n = (int)params.size();
-  std::vector<long> offs(n);
-  std::vector<float*> wps(n);
-  std::vector<float> lrms(n), dcms(n);
-  for (int i = 0; i < n; ++i) {
-    offs[i] = params[i].offset;
-    wps[i] = params[i].blob->mutable_gpu_data();
-    lrms[i] = params[i].lr_mult;
-    dcms[i] = params[i].decay_mult;
-  }
-  d_seg_off_ = (long*)E.dalloc.alloc(n * sizeof(long));
-  d_w_ptrs_ = (float**)E.dalloc.alloc(n * sizeof(float*));
-  d_lrs_ = (float*)E.dalloc.alloc(n * sizeof(float));
-  d_decays_ = (float*)E.dalloc.alloc(n * sizeof(float));
-  HIP_CHECK(hipMemcpy(d_seg_off_, offs.data(), n * sizeof(long),
-                      hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_w_ptrs_, wps.data(), n * sizeof(float*),
-                      hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_lrs_, lrms.data(), n * sizeof(float),
-                      hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_decays_, dcms.data(), n * sizeof(float),
-                      hipMemcpyHostToDevice));
-  if (clipping()) {
-    // a bucket's grid is at most the sum of its params' grids (ceil and the
-    // block cap are both subadditive), so this holds any bucketing
-    for (int i = 0; i < n; ++i)
-      clip_partials_cap_ +=
-          gpu::grad_sumsq_partials((long)padded(params[i].count));
-    clip_partials_.reserve(sizeof(double) * clip_partials_cap_);
-    clip_slot_.reserve(2 * sizeof(float));
-  }
+void Reducer::param_ready(int param_id, hipEvent_t done) {
+  CHECK_EQ_((long)param_id, bucket_end_) << "params must arrive in order";
+  bucket_end_ = param_id + 1;
+  const auto [lo, hi] = range(bucket_start_, bucket_end_);
+  if (hi - lo >= solver_->bucket_budget_) flush(done);
 }
 
 void Reducer::flush(hipEvent_t ev) {
@@ -324,28 +313,24 @@ void Reducer::flush(hipEvent_t ev) {
   Solver& S = *solver_;
   Engine& E = Engine::get();
   auto& params = S.net().learnable_params();
-  const auto& first = params[bucket_start_];
-  const auto& last = params[bucket_end_ - 1];
-  const long count = last.offset + (long)padded(last.count) - first.offset;
+  const auto [lo, hi] = range(bucket_start_, bucket_end_);
   if (E.mode == Mode::GPU) {
     if (ev) HIP_CHECK(hipStreamWaitEvent(E.comm_stream, ev, 0));
-    if (S.comm_ && S.comm_->world() > 1) {
-      PerfScope ps("allreduce", E.comm_stream, 0, 2.0 * count * 4);
-      S.comm_->allreduce(S.net().diff_arena() + first.offset, count,
-                         E.comm_stream);
+    if (S.world() > 1) {
+      PerfScope ps("allreduce", E.comm_stream, 0, 2.0 * (hi - lo) * 4);
+      S.comm_->allreduce(S.net().diff_arena() + lo, hi - lo, E.comm_stream);
     }
     if (S.clipping()) {
       // the bucket's share of the global norm, behind its all-reduce on the
       // comm stream; its update waits for the factor (iteration_end)
-      S.ensure_seg_table();
-      const int nb = gpu::grad_sumsq_partials(count);
-      CHECK_LE_(partials_ + nb, S.clip_partials_cap_);
+      const int nb = gpu::grad_sumsq_partials(hi - lo);
+      CHECK_LE_(partials_ + nb, S.tables_.clip_partials_cap);
       partials_ += gpu::grad_sumsq(
-          E.comm_stream, S.net().diff_arena(), first.offset,
-          first.offset + count, (double*)S.clip_partials_.p + partials_);
+          E.comm_stream, S.net().diff_arena(), lo, hi,
+          S.tables_.clip_partials.as<double>() + partials_);
     }
   } else {
-    if (S.comm_ && S.comm_->world() > 1) {
+    if (S.world() > 1) {
       // CPU buckets: gather the param diffs into one flat range is
       // unnecessary — host diffs are per-blob; reduce each param
       for (long k = bucket_start_; k < bucket_end_; ++k)
@@ -376,32 +361,30 @@ void Reducer::update(long begin, long end) {
   Solver& S = *solver_;
   Engine& E = Engine::get();
   auto& params = S.net().learnable_params();
-  const auto& first = params[begin];
-  const auto& last = params[end - 1];
-  const long count = last.offset + (long)padded(last.count) - first.offset;
   if (E.mode == Mode::GPU) {
+    const auto [lo, hi] = range(begin, end);
+    const Solver::UpdateTables& T = S.tables_;
     const float* factor =
-        S.clipping() ? (const float*)S.clip_slot_.p + 1 : nullptr;
-    // bucket-fused update: one launch over the flat arena range
-    S.ensure_seg_table();
+        S.clipping() ? T.clip_slot.as<const float>() + 1 : nullptr;
     // the kernel writes the weights through the table's cached pointers,
     // behind the blobs' backs: mark each blob's device copy as the newer
     // one, or a host copy made by an earlier read (param get, snapshot)
     // would be served again, stale, after this update
     for (long k = begin; k < end; ++k)
       params[k].blob->mutable_gpu_data();
+    // bucket-fused update: one launch over the flat arena range
     if (S.rule_ == kRuleSgd && !S.l1_)
       gpu::sgd_update_segmented(
-          E.comm_stream, first.offset, first.offset + count,
-          S.net().diff_arena(), S.history(), S.d_seg_off_, S.d_w_ptrs_,
-          S.d_lrs_, S.d_decays_, (int)params.size(), S.cur_mom_, S.cur_lr_,
+          E.comm_stream, lo, hi, S.net().diff_arena(), S.history(),
+          T.seg_off.as<long>(), T.w_ptrs.as<float*>(), T.lrs.as<float>(),
+          T.decays.as<float>(), T.nseg, S.cur_mom_, S.cur_lr_,
           S.weight_decay_, S.grad_scale_, factor);
     else
       gpu::solver_update_segmented(
-          E.comm_stream, S.rule_, S.l1_, first.offset, first.offset + count,
-          S.net().diff_arena(), S.history(0), S.history(1), S.d_seg_off_,
-          S.d_w_ptrs_, S.d_lrs_, S.d_decays_, (int)params.size(), S.coef(),
-          factor);
+          E.comm_stream, S.rule_, S.l1_, lo, hi, S.net().diff_arena(),
+          S.history(0), S.history(1), T.seg_off.as<long>(),
+          T.w_ptrs.as<float*>(), T.lrs.as<float>(), T.decays.as<float>(),
+          T.nseg, S.coef(), factor);
   } else {
     for (long k = begin; k < end; ++k) {
       const auto& p = params[k];
@@ -420,15 +403,15 @@ void Reducer::iteration_end(hipEvent_t backward_done) {
   Engine& E = Engine::get();
   Solver& S = *solver_;
   if (S.clipping()) {
-    const int world = S.comm_ && S.comm_->world() > 1 ? S.comm_->world() : 1;
     if (E.mode == Mode::GPU) {
-      // (a net without learnable params has no bucket, no slot, no launch)
+      // (a net without learnable params has no bucket and no launch)
       if (partials_ > 0)
-        gpu::clip_finalize(E.comm_stream, (const double*)S.clip_partials_.p,
-                           partials_, world, S.clip_,
-                           (float*)S.clip_slot_.p);
+        gpu::clip_finalize(E.comm_stream,
+                           S.tables_.clip_partials.as<const double>(),
+                           partials_, S.world(), S.clip_,
+                           S.tables_.clip_slot.as<float>());
     } else {
-      S.clip_norm_ = (float)(std::sqrt(sumsq_) / world);
+      S.clip_norm_ = (float)(std::sqrt(sumsq_) / S.world());
       S.clip_factor_ = clip_factor(S.clip_norm_, S.clip_);
     }
     for (const auto& b : deferred_) update(b.first, b.second);
@@ -436,12 +419,10 @@ void Reducer::iteration_end(hipEvent_t backward_done) {
     ++S.clip_iters_;
   }
   if (E.mode == Mode::GPU) {
-    if (!comm_done_ev_)
-      HIP_CHECK(
-          hipEventCreateWithFlags(&comm_done_ev_, hipEventDisableTiming));
-    HIP_CHECK(hipEventRecord(comm_done_ev_, E.comm_stream));
+    comm_done_ev_.create();
+    HIP_CHECK(hipEventRecord(comm_done_ev_.get(), E.comm_stream));
     // next iteration's forward must see the updated weights
-    HIP_CHECK(hipStreamWaitEvent(E.stream, comm_done_ev_, 0));
+    HIP_CHECK(hipStreamWaitEvent(E.stream, comm_done_ev_.get(), 0));
   }
 }
 
@@ -493,9 +474,7 @@ void Solver::Step(int iters) {
       upd_lr_ *= std::sqrt(1.f - std::pow(aux_, t)) /
                  (1.f - std::pow(cur_mom_, t));
     }
-    const float world =
-        comm_ && comm_->world() > 1 ? (float)comm_->world() : 1.f;
-    grad_scale_ = 1.f / (world * (float)iter_size);
+    grad_scale_ = 1.f / ((float)world() * (float)iter_size);
     reducer_.start_iteration();
     if (iter_size == 1) {
       E.data_iter = (uint64_t)iter_;
@@ -559,10 +538,11 @@ void Solver::grad_norm(float* norm, float* factor) {
   CHECK_(clip_iters_ > 0) << "grad_norm: no iteration has finished yet";
   Engine& E = Engine::get();
   float nf[2] = {clip_norm_, clip_factor_};
-  if (E.mode == Mode::GPU && clip_slot_.p) {
+  if (E.mode == Mode::GPU && tables_.clip_slot.p) {
     // the finalize and the updates run on the comm stream
     HIP_CHECK(hipStreamSynchronize(E.comm_stream));
-    HIP_CHECK(hipMemcpy(nf, clip_slot_.p, sizeof(nf), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(nf, tables_.clip_slot.p, sizeof(nf),
+                        hipMemcpyDeviceToHost));
   }
   *norm = nf[0];
   *factor = nf[1];

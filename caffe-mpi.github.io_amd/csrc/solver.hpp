@@ -51,24 +51,21 @@ class Solver;
 
 // Solver state in diff-arena layout (SGD history, the iter_size
 // accumulator): zero-filled floats that live on the device in GPU mode and
-// in a host vector in CPU mode.  Device memory comes from Engine::dalloc
-// and goes back to it in the destructor, without a HIP call.
+// in a host vector in CPU mode.  The device side is a DeviceBuf: the solver
+// that owns it waits before it goes back to the allocator.
 class StateBuf {
  public:
-  StateBuf() = default;
-  StateBuf(const StateBuf&) = delete;
-  StateBuf& operator=(const StateBuf&) = delete;
-  ~StateBuf();
   void alloc(long count);  // once; zero-filled on the compute stream
   bool empty() const { return count_ == 0; }
-  float* ptr() { return dev_ ? dev_ : host_.data(); }  // null while empty
+  // null while empty
+  float* ptr() { return dev_.p ? dev_.as<float>() : host_.data(); }
   // blocking copies out of and into [offset, offset + count)
   void read(long offset, long count, float* out);
   void write(long offset, const float* in, long count);
   void zero();  // on the compute stream
 
  private:
-  float* dev_ = nullptr;
+  DeviceBuf dev_;
   std::vector<float> host_;
   long count_ = 0;
 };
@@ -85,16 +82,17 @@ class Reducer : public ReduceHook {
   void start_iteration();
   void param_ready(int param_id, hipEvent_t done) override;
   void iteration_end(hipEvent_t backward_done) override;
-  hipEvent_t comm_done() { return comm_done_ev_; }
 
  private:
   void flush(hipEvent_t ev);
   // the update of params [begin, end), one bucket
   void update(long begin, long end);
+  // the padded arena range [lo, hi) of params [begin, end), one bucket
+  std::pair<long, long> range(long begin, long end) const;
   Solver* solver_;
   long bucket_start_ = 0;   // param index where current bucket starts
   long bucket_end_ = 0;     // one past last ready param
-  hipEvent_t comm_done_ev_ = nullptr;
+  GpuEvent comm_done_ev_;   // created at the first GPU iteration's end
   // clip_gradients: the buckets whose update waits for the factor, in
   // arrival order, and the iteration's sum of squares so far — partials
   // written to the solver's device buffer, or the host sum in CPU mode
@@ -164,7 +162,10 @@ class Solver {
   // slot the rule does not have
   float* history(int slot = 0) { return history_[slot].ptr(); }
   void bcast_weights();  // initial weight broadcast (parallel.cpp:208-227)
+  ~Solver();  // waits: updates may still run on the comm stream
 
+ private:
+  int world() const { return comm_ && comm_->world() > 1 ? comm_->world() : 1; }
   // per-iteration cached coefficients for the fused update
   float cur_lr_ = 0.f, cur_mom_ = 0.f, weight_decay_ = 0.f;
   float grad_scale_ = 1.f;
@@ -181,7 +182,6 @@ class Solver {
                       grad_scale_ * clip_factor_, aux_, delta_};
   }
 
- private:
   PMsgPtr param_;
   PMsgPtr net_msg_;
   std::unique_ptr<Net> net_;
@@ -207,20 +207,23 @@ class Solver {
   float aux_ = 0.f;    // RMSProp rms_decay / Adam momentum2
   float delta_ = 0.f;  // the rule's clamped delta
   void parse_type();
-  // device segment table for the bucket-fused update (GPU mode): arena
-  // offsets, per-param weight base pointers, lr/decay (mults folded in at
-  // flush time by scaling the per-iteration coefficients)
-  long* d_seg_off_ = nullptr;
-  float** d_w_ptrs_ = nullptr;
-  float* d_lrs_ = nullptr;    // per-param lr MULTIPLIERS (uploaded once)
-  float* d_decays_ = nullptr; // per-param decay multipliers
-  void ensure_seg_table();
-  // clip_gradients (GPU mode), allocated once with the segment table: one
-  // double per block of every bucket's sum-of-squares launch, and the
-  // {norm, factor} slot the finalize writes and the updates read
+  // What the bucket updates read on the device (GPU mode), built once at
+  // construction.  The segment table of the bucket-fused update, one entry
+  // per learnable param: arena offset, weight base pointer, lr and decay
+  // MULTIPLIERS (immutable after the net build; the per-iteration rate and
+  // decay are kernel arguments, so no H2D copy runs in the iteration loop).
+  // With clip_gradients also one double per block of every bucket's sum-of-
+  // squares launch, and the {norm, factor} slot the finalize writes and the
+  // updates read.
+  struct UpdateTables {
+    int nseg = 0;
+    DeviceBuf seg_off, w_ptrs, lrs, decays;  // long, float*, float, float
+    DeviceBuf clip_partials, clip_slot;      // double, float[2]
+    int clip_partials_cap = 0;
+    void build(Net& net, bool clipping);
+  };
+  UpdateTables tables_;
   float clip_ = -1.f;
-  DeviceBuf clip_partials_, clip_slot_;
-  int clip_partials_cap_ = 0;
   long clip_iters_ = 0;  // iterations that went through the clip path
   void report_clipping();
   // iter_size accumulation buffer (diff-arena layout; only allocated when

@@ -188,6 +188,10 @@ int caffe_net_param_set(caffe_net_t n, int idx, const float* in, long count);
 
 /* device + perf introspection */
 int caffe_device_synchronize(void);
+/* device bytes the engine's caching allocator has handed out and not got
+ * back, as requested; blocks it caches for reuse are not counted.  Back at
+ * its earlier value after caffe_solver_free / caffe_net_free. */
+size_t caffe_device_live_bytes(void);
 /* perf counters per kernel class: returns number of classes; each row of
  * `names` gets a \0-terminated class name (cap bytes), and launches /
  * flops / bytes / ns land in the parallel arrays */
