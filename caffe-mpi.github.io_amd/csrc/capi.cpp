@@ -3,10 +3,6 @@
 #include "../../include/caffe_amd.h"
 #include "solver.hpp"
 
-namespace camd {
-extern int g_syn_shape[3];  // defined in layers_cpu.cpp
-}
-
 using namespace camd;
 
 namespace {
@@ -111,10 +107,9 @@ int caffe_set_random_seed(uint64_t seed) {
 
 int caffe_set_synthetic_shape(int c, int h, int w, int num_classes) {
   API_TRY
-  camd::g_syn_shape[0] = c;
-  camd::g_syn_shape[1] = h;
-  camd::g_syn_shape[2] = w;
-  if (num_classes > 0) Engine::get().syn_classes = num_classes;
+  Engine& E = Engine::get();
+  E.syn_shape = {c, h, w};
+  if (num_classes > 0) E.syn_classes = num_classes;
   return 0;
   API_CATCH
 }

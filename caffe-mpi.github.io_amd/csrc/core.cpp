@@ -106,6 +106,20 @@ DeviceBuf::~DeviceBuf() {
   if (p) Engine::get().dalloc.release(p, bytes);
 }
 
+void* PinnedBuf::reserve(size_t want) {
+  if (want > bytes) {
+    if (p) HIP_CHECK(hipHostFree(p));
+    p = nullptr;
+    bytes = 0;
+    HIP_CHECK(hipHostMalloc(&p, want));
+    bytes = want;
+  }
+  return p;
+}
+PinnedBuf::~PinnedBuf() {
+  if (p) (void)hipHostFree(p);
+}
+
 SyncedMemory::~SyncedMemory() {
   if (cpu_ptr_) free(cpu_ptr_);
   if (gpu_ptr_ && own_gpu_)

@@ -14,6 +14,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -152,6 +153,25 @@ struct DeviceBuf {
   ~DeviceBuf();
 };
 
+// Pinned host memory that one object owns (the data feed's upload staging):
+// copies out of it are truly asynchronous, so it may be the source of a copy
+// still in flight.  Same rules as DeviceBuf: grows only when asked for more
+// (the old contents are dropped), never waits; its owner is destroyed after
+// the Engine::sync() of the object above it.
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  void* reserve(size_t want);  // p, grown first when want > bytes
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf();
+};
+
 // A hipEvent_t (timing disabled) that one object owns; move-only.  Default-
 // constructed it holds no event (CPU mode, vector elements before create()).
 class GpuEvent {
@@ -210,6 +230,7 @@ class Engine {
   // synthetic-data configuration (no LMDB datasets in this environment)
   bool synthetic = true;
   int syn_classes = 1000;
+  std::array<int, 3> syn_shape{};  // C, H, W; H == 0: not set
   // current training iteration (set by Solver::Step) — synthetic data and
   // dropout masks key off this so snapshot/restore resumes the exact
   // stream (the reference's LMDB cursor position analog)

@@ -2238,15 +2238,15 @@ void shared_diff_sum(hipStream_t s, long lo, long hi, float* g_arena,
   ktrace(kSharedDiffSum, kVarNone, lo, hi, nseg, nsrc);
 }
 
-// ---------------------------------------------------- LMDB transform
+// ----------------------------------------------- data feed transform
 // uint8 -> fp32 crop/mirror/mean/scale (reference data_transformer.cu:
-// 14-100): one thread per output element; geo = per-image (ho, wo,
-// mirror); mean subtracted in SOURCE coordinates (mean_file semantics).
+// 14-100): one thread per output element, transform_u8_at (math.hpp) on
+// its image; geo = per-image (ho, wo, mirror).
 __global__ void k_transform_u8(const uint8_t* __restrict__ in, int N,
                                int C, int inH, int inW, int outH, int outW,
                                const int* __restrict__ geo,
                                const float* __restrict__ mean,
-                               int mean_mode, float scale,
+                               MeanMode mean_mode, float scale,
                                float* __restrict__ out) {
   const long total = (long)N * C * outH * outW;
   GRID_STRIDE(i, total) {
@@ -2254,20 +2254,14 @@ __global__ void k_transform_u8(const uint8_t* __restrict__ in, int N,
     const int y = (int)((i / outW) % outH);
     const int c = (int)((i / ((long)outW * outH)) % C);
     const int n = (int)(i / ((long)outW * outH * C));
-    const int ho = geo[3 * n], wo = geo[3 * n + 1], mir = geo[3 * n + 2];
-    const int sx = wo + (mir ? outW - 1 - x : x);
-    const long src = (((long)n * C + c) * inH + ho + y) * inW + sx;
-    float m = 0.f;
-    if (mean_mode == 1)
-      m = mean[c];
-    else if (mean_mode == 2)
-      m = mean[((long)c * inH + ho + y) * inW + sx];
-    out[i] = ((float)in[src] - m) * scale;
+    out[i] = transform_u8_at(in + (long)n * C * inH * inW, c, y, x,
+                             geo[3 * n], geo[3 * n + 1], geo[3 * n + 2], inH,
+                             inW, outW, mean, mean_mode, scale);
   }
 }
 void transform_u8(hipStream_t s, const uint8_t* in, int N, int C, int inH,
                   int inW, int outH, int outW, const int* geo,
-                  const float* mean, int mean_mode, float scale,
+                  const float* mean, MeanMode mean_mode, float scale,
                   float* out) {
   const long total = (long)N * C * outH * outW;
   PerfScope perf(PERF_CLASS("data"), s, 0, 5.0 * total);
@@ -2282,10 +2276,9 @@ __global__ void k_fill_uniform(long n, uint64_t key, float lo, float hi,
   GRID_STRIDE(i, n)
   y[i] = lo + (hi - lo) * d_u01(d_splitmix64(key ^ (uint64_t)i));
 }
-void fill_uniform(hipStream_t s, long n, uint64_t seed, uint64_t counter,
-                  float lo, float hi, float* y) {
+void fill_uniform(hipStream_t s, long n, uint64_t seed, float lo, float hi,
+                  float* y) {
   PerfScope perf(PERF_CLASS("data"), s, 0, 4.0 * n);
-  (void)counter;
   hipLaunchKernelGGL(k_fill_uniform, dim3(nblocks(n, 4)), dim3(TPB), 0, s,
                      n, seed, lo, hi, y);
 }
@@ -2296,9 +2289,8 @@ __global__ void k_fill_labels(long n, uint64_t key, int classes,
   y[i] = (float)(d_splitmix64(key ^ 0xABCDull ^ (uint64_t)i) %
                  (uint64_t)classes);
 }
-void fill_labels(hipStream_t s, long n, uint64_t seed, uint64_t counter,
-                 int classes, float* y) {
-  (void)counter;
+void fill_labels(hipStream_t s, long n, uint64_t seed, int classes,
+                 float* y) {
   hipLaunchKernelGGL(k_fill_labels, dim3(nblocks(n)), dim3(TPB), 0, s, n,
                      seed, classes, y);
 }

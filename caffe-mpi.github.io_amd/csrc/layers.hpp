@@ -163,10 +163,10 @@ struct Workspace {
 };
 
 // ------------------------------------------------------------- layer classes
-struct LmdbFeed;  // data_lmdb.cpp: reader + prefetch + transform state
+struct DataFeed;  // data_feed.cpp: record source + prefetch + transform
 
-class DataLayer : public Layer {  // synthetic or LMDB source (§8a a12,
-                                  // §8f.1)
+class DataLayer : public Layer {  // synthetic stream, or a feed (LMDB here,
+                                  // an image list in ImageDataLayer)
  public:
   using Layer::Layer;
   void LayerSetUp(const std::vector<Blob*>&,
@@ -187,14 +187,9 @@ class DataLayer : public Layer {  // synthetic or LMDB source (§8a a12,
   int max_bottom_blobs() const override { return 0; }
 
   int batch_ = 0, C_ = 3, H_ = 224, W_ = 224;
-  uint64_t iter_ = 0;
-
-  // LMDB mode (data_param.source exists on disk — else synthetic):
-  // from-scratch reader + prefetch worker + GPU uint8 transform
-  void setup_lmdb(const std::string& source);
-  void forward_lmdb_cpu(const std::vector<Blob*>& top);
-  void forward_lmdb_gpu(const std::vector<Blob*>& top);
-  std::shared_ptr<LmdbFeed> feed_;  // owns its device upload buffers
+  // set when data_param.source exists on disk (else the synthetic stream);
+  // owns its staging buffers, gives the top shape at setup
+  std::shared_ptr<DataFeed> feed_;
 };
 
 class ConvolutionLayer : public Layer {

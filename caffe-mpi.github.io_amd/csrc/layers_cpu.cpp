@@ -3,8 +3,6 @@
 // parity is checked against oracle/, never against this file).
 #include <cmath>
 
-#include <sys/stat.h>
-
 #include "layers.hpp"
 
 namespace camd {
@@ -144,75 +142,6 @@ Workspace::~Workspace() {
     if (b.p && !b.device) free(b.p);
 }
 
-
-// ---------------------------------------------------------------- Data
-void DataLayer::LayerSetUp(const std::vector<Blob*>&,
-                           const std::vector<Blob*>&) {
-  auto dp = param_->sub("data_param");
-  batch_ = dp ? (int)dp->inum("batch_size", 1) : 1;
-  // LMDB source when data_param.source EXISTS on disk (reference
-  // db_lmdb.cpp backend); a prototxt naming an absent dataset falls back
-  // to the synthetic stream so the reference model zoo runs unmodified
-  // in this dataset-less environment (round-1 drop-in contract)
-  const std::string src = dp ? dp->str("source", "") : "";
-  if (!src.empty()) {
-    struct stat st {};
-    if (stat(src.c_str(), &st) == 0) {
-      setup_lmdb(src);
-      return;
-    }
-    fprintf(stderr,
-            "[caffe_amd] DataLayer '%s': source '%s' not found — using "
-            "the synthetic stream\n",
-            name_.c_str(), src.c_str());
-  }
-  auto tp = param_->sub("transform_param");
-  const int crop = tp ? (int)tp->inum("crop_size", 0) : 0;
-  // synthetic shape: explicit engine override, else crop_size (3 channels)
-  extern int g_syn_shape[3];
-  if (g_syn_shape[1] > 0) {
-    C_ = g_syn_shape[0];
-    H_ = g_syn_shape[1];
-    W_ = g_syn_shape[2];
-  } else if (crop > 0) {
-    C_ = 3;
-    H_ = W_ = crop;
-  } else {
-    CAMD_FATAL << "DataLayer '" << name_
-               << "': no crop_size and no synthetic shape set "
-                  "(caffe_set_synthetic_shape)";
-  }
-}
-int g_syn_shape[3] = {0, 0, 0};
-
-void DataLayer::Reshape(const std::vector<Blob*>&,
-                        const std::vector<Blob*>& top) {
-  top[0]->Reshape({batch_, C_, H_, W_});
-  if (top.size() > 1) top[1]->Reshape({batch_});
-}
-
-void DataLayer::Forward_cpu(const std::vector<Blob*>&,
-                            const std::vector<Blob*>& top) {
-  if (feed_) {
-    forward_lmdb_cpu(top);
-    ++iter_;
-    return;
-  }
-  Engine& E = Engine::get();
-  const uint64_t key = h_splitmix64(E.seed ^ ((uint64_t)E.rank << 40) ^
-                                  (E.data_iter << 8));
-  float* d = top[0]->mutable_cpu_data();
-  const long n = top[0]->count();
-  for (long i = 0; i < n; ++i)
-    d[i] = h_u01(h_splitmix64(key ^ (uint64_t)i)) * 2.f - 1.f;
-  if (top.size() > 1) {
-    float* l = top[1]->mutable_cpu_data();
-    for (long i = 0; i < batch_; ++i)
-      l[i] = (float)(h_splitmix64(key ^ 0xABCDull ^ (uint64_t)i) %
-                     (uint64_t)E.syn_classes);
-  }
-  ++iter_;
-}
 
 // ---------------------------------------------------------------- Conv
 void ConvolutionLayer::LayerSetUp(const std::vector<Blob*>& bottom,

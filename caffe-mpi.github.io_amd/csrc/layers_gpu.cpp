@@ -14,24 +14,6 @@ namespace camd {
 using gpu::GemmEpi;
 using gpu::GemmView;
 
-void DataLayer::Forward_gpu(const std::vector<Blob*>&,
-                            const std::vector<Blob*>& top) {
-  if (feed_) {
-    forward_lmdb_gpu(top);
-    ++iter_;
-    return;
-  }
-  Engine& E = Engine::get();
-  const uint64_t key =
-      h_splitmix64(E.seed ^ ((uint64_t)E.rank << 40) ^ (E.data_iter << 8));
-  gpu::fill_uniform(E.stream, top[0]->count(), key, 0, -1.f, 1.f,
-                    top[0]->mutable_gpu_data());
-  if (top.size() > 1)
-    gpu::fill_labels(E.stream, top[1]->count(), key, 0, E.syn_classes,
-                     top[1]->mutable_gpu_data());
-  ++iter_;
-}
-
 // ------------------------------------------------------------------ Conv
 // MI355X-first conv, two paths:
 //  - IMPLICIT GEMM: the GEMM staging reads x / dY straight from NCHW through

@@ -153,6 +153,28 @@ CAMD_HD inline float contrastive_row_beta(float dsq, bool similar,
   return mdist > 0.f ? -alpha * mdist / (d + 1e-4f) : 0.f;
 }
 
+// ------------------------------------------------------ data feed transform
+// One output value of the uint8 crop/mirror/mean/scale transform (the
+// reference's DataTransformer::Transform): im is one record [C][inH][inW],
+// (c, y, x) the destination position in the crop at (ho, wo), outW wide; mir
+// reads the source row right to left.  The mean is subtracted in SOURCE
+// coordinates (mean_file semantics).  uint8 converts exactly and a subtract
+// then a multiply has no fused form: CPU loop and kernel give the same bits.
+enum MeanMode { kMeanNone = 0, kMeanPerChannel, kMeanPerPixel };
+CAMD_HD inline float transform_u8_at(const uint8_t* im, int c, int y, int x,
+                                     int ho, int wo, int mir, int inH,
+                                     int inW, int outW, const float* mean,
+                                     MeanMode mean_mode, float scale) {
+  const int sx = wo + (mir ? outW - 1 - x : x);
+  const long src = ((long)c * inH + ho + y) * inW + sx;
+  float m = 0.f;
+  if (mean_mode == kMeanPerChannel)
+    m = mean[c];
+  else if (mean_mode == kMeanPerPixel)
+    m = mean[src];
+  return ((float)im[src] - m) * scale;
+}
+
 // --------------------------------------------------------- exact fast division
 // n / d for 0 <= n < 2^31 and 1 <= d <= 2^31 as multiply-high, add and shift
 // (Granlund & Montgomery's round-up form: with l = ceil(log2 d) and
@@ -481,18 +503,16 @@ void shared_diff_sum(hipStream_t s, long lo, long hi, float* g_arena,
                      const long* seg_off, int nseg, const int* src_begin,
                      const float* const* srcs, int nsrc);
 
-// LMDB batch transform: uint8 -> fp32 crop/mirror/mean/scale
-// (data_transformer.cu:14-100 analog); geo = per-image (ho, wo, mirror),
-// mean_mode 0 = none, 1 = per-channel, 2 = per-pixel (mean_file)
+// Data feed batch transform: transform_u8_at at every output element
+// (data_transformer.cu:14-100 analog); geo = per-image (ho, wo, mirror)
 void transform_u8(hipStream_t s, const uint8_t* in, int N, int C, int inH,
                   int inW, int outH, int outW, const int* geo,
-                  const float* mean, int mean_mode, float scale,
+                  const float* mean, MeanMode mean_mode, float scale,
                   float* out);
 
-void fill_uniform(hipStream_t s, long n, uint64_t seed, uint64_t counter,
-                  float lo, float hi, float* y);
-void fill_labels(hipStream_t s, long n, uint64_t seed, uint64_t counter,
-                 int classes, float* y);
+void fill_uniform(hipStream_t s, long n, uint64_t seed, float lo, float hi,
+                  float* y);
+void fill_labels(hipStream_t s, long n, uint64_t seed, int classes, float* y);
 
 }  // namespace gpu
 }  // namespace camd

@@ -121,10 +121,6 @@ static void setup_device(const std::map<std::string, std::string>& flags) {
   Engine::get().set_mode_gpu(dev);
 }
 
-namespace camd {
-extern int g_syn_shape[3];
-}
-
 // ---- multi-GPU train (`-gpu=all` / `-gpu=0,1,...`): the reference's
 // in-process thread-per-GPU P2PManager (parallel.cpp) is replaced by the
 // MI355X-native one-process-per-GPU model — the parent forks one worker per
@@ -367,10 +363,9 @@ int main(int argc, char** argv) {
   if (const char* ss = getenv("CAFFE_SYN_SHAPE")) {
     int c = 0, h = 0, w = 0, k = 0;
     if (sscanf(ss, "%dx%dx%dx%d", &c, &h, &w, &k) >= 3) {
-      camd::g_syn_shape[0] = c;
-      camd::g_syn_shape[1] = h;
-      camd::g_syn_shape[2] = w;
-      if (k > 0) Engine::get().syn_classes = k;
+      Engine& E = Engine::get();
+      E.syn_shape = {c, h, w};
+      if (k > 0) E.syn_classes = k;
     }
   }
   if (argc < 2) {

@@ -93,6 +93,42 @@ def test_net_free_returns_every_byte(net, tmp_path):
     assert_cycles_return_to_baseline(lambda: net_cycle(str(path)))
 
 
+def test_data_feed_net_free_returns_every_byte(tmp_path):
+    """A Data layer on an LMDB owns pinned staging, two events and three
+    device buffers (uint8 batch, geometry, mean); three forwards use both
+    staging parities and wait once on an event."""
+    import os
+    import sys
+    from engine_util import REPO
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    from make_lmdb import make_lmdb
+    make_lmdb(str(tmp_path / "db"), 8, 3, 8, 8, 5)
+    path = tmp_path / "feed.prototxt"
+    path.write_text(f"""name: "feed"
+layer {{ name: "data" type: "Data" top: "data" top: "label"
+  data_param {{ source: "{tmp_path}/db" batch_size: 4 backend: LMDB }}
+  transform_param {{ mean_value: 104 mean_value: 117 mean_value: 123 }} }}
+layer {{ name: "ip" type: "InnerProduct" bottom: "data" top: "fc"
+  inner_product_param {{ num_output: 10
+    weight_filler {{ type: "gaussian" std: 0.05 }} }} }}
+layer {{ name: "loss" type: "SoftmaxWithLoss" bottom: "fc" bottom: "label"
+  top: "loss" }}
+""")
+
+    def cycle():
+        net = ca.Net.from_file(str(path))
+        for it in range(3):
+            ca.set_data_iter(it)
+            net.forward()
+        assert np.isfinite(net.loss())
+        ca._lib.caffe_net_free(net._h)
+
+    try:
+        assert_cycles_return_to_baseline(cycle)
+    finally:
+        ca.set_data_iter(0)
+
+
 def test_live_bytes_counts_a_live_solver():
     solver_cycle("sgd")  # workspace growth
     before = ca.device_live_bytes()

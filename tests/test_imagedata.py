@@ -121,6 +121,35 @@ def test_shuffle_epoch_coverage(dataset):
                           np.asarray(net2.blob("data")))
 
 
+# The shuffle over two epochs of the 9-image dataset at seed 3, batch 3,
+# iterations 0..5, rank 0: the list positions read and their labels
+# (position % 4).  Recorded by running exactly this test's loop on the commit
+# before the permutation moved from ImageDataLayer into ImageListSource and
+# printing `order` and `labels`; the order depends only on the seed, the key
+# constant of the shuffle and splitmix64.
+SHUFFLE_ORDER = [6, 4, 1, 2, 0, 8, 7, 3, 5, 4, 1, 6, 3, 2, 0, 7, 8, 5]
+SHUFFLE_LABELS = [2, 0, 1, 2, 0, 0, 3, 3, 1, 0, 1, 2, 3, 2, 0, 3, 0, 1]
+
+
+def test_shuffle_order_is_pinned(dataset):
+    d, imgs = dataset
+    ca.set_mode("cpu")
+    ca.set_random_seed(3)
+    net = net_from_text(img_net(d, batch=3, extra="shuffle: true"))
+    order, labels = [], []
+    for it in range(6):
+        ca.set_data_iter(it)
+        net.forward()
+        data = np.asarray(net.blob("data")).reshape(3, 3, 10, 12)
+        labels += [int(v) for v in np.asarray(net.blob("label")).ravel()]
+        for j in range(3):
+            order += [i for i, im in enumerate(imgs)
+                      if np.array_equal(data[j], im.astype(np.float32))]
+    assert labels == SHUFFLE_LABELS
+    assert order == SHUFFLE_ORDER
+    assert order[:9] != order[9:]  # the second epoch is reshuffled
+
+
 def test_pgm_grayscale(tmp_path):
     a = np.random.default_rng(1).integers(0, 256, (1, 7, 9),
                                           dtype=np.uint8)

@@ -231,6 +231,90 @@ def test_lmdb_gpu_transform_parity(db):
     assert relerr(outs["gpu"], outs["cpu"]) < 1e-6
 
 
+def binaryproto_mean(path, mean):
+    # BlobProto: field 7 shape{dim}, field 5 packed float data
+    from make_lmdb import varint
+    shape_msg = b"".join(b"\x08" + varint(d) for d in mean.shape)
+    data = mean.ravel().tobytes()
+    path.write_bytes(b"\x3a" + varint(len(shape_msg)) + shape_msg +
+                     b"\x2a" + varint(len(data)) + data)
+
+
+MODES_SHAPE = (3, 10, 13)  # non-square: a swapped H/W shows
+
+
+@pytest.fixture(scope="module")
+def modes_db(tmp_path_factory):
+    d = tmp_path_factory.mktemp("lmdb_modes")
+    make_lmdb(str(d / "db"), 11, *MODES_SHAPE, SEED)
+    mean = np.random.default_rng(78).uniform(0, 255, MODES_SHAPE)
+    binaryproto_mean(d / "mean.binaryproto", mean.astype(np.float32))
+    return str(d / "db"), str(d / "mean.binaryproto")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("geometry", ["train_crop_mirror", "test_crop",
+                                      "train_full_mirror"])
+@pytest.mark.parametrize("mean", ["none", "mean_value", "mean_file"])
+def test_lmdb_gpu_transform_modes(modes_db, mean, geometry):
+    # every mean mode of k_transform_u8 under every geometry, bit for bit
+    # against the CPU loop: both run transform_u8_at on uint8 inputs, which
+    # convert exactly, and a subtract then a multiply has no fused form.
+    # Four iterations reuse each pinned parity once behind its event; 11
+    # records at batch 4 wrap the epoch.
+    db, mean_file = modes_db
+    tp = "scale: 0.0078125\n"
+    tp += {"none": "", "mean_file": f'    mean_file: "{mean_file}"\n',
+           "mean_value": "    mean_value: 104\n    mean_value: 117\n"
+                         "    mean_value: 123\n"}[mean]
+    tp += {"train_crop_mirror": "    crop_size: 7\n    mirror: true\n",
+           "test_crop": "    crop_size: 7\n",
+           "train_full_mirror": "    mirror: true\n"}[geometry]
+    phase = "TEST" if geometry == "test_crop" else "TRAIN"
+    text = f"""name: "t"
+layer {{
+  name: "data" type: "Data" top: "data" top: "label"
+  include {{ phase: {phase} }}
+  data_param {{ source: "{db}" batch_size: 4 backend: LMDB }}
+  transform_param {{
+    {tp}  }}
+}}
+"""
+    nets = {}
+    for mode in ("cpu", "gpu"):
+        ca.set_mode(mode)
+        ca.set_random_seed(31)
+        nets[mode] = net_from_text(text, phase=int(phase == "TEST"))
+    for it in range(4):
+        ca.set_data_iter(it)
+        out = {}
+        for mode in ("cpu", "gpu"):
+            ca.set_mode(mode)
+            nets[mode].forward()
+            out[mode] = (np.asarray(nets[mode].blob("data")).copy(),
+                         np.asarray(nets[mode].blob("label")).copy())
+        assert np.array_equal(out["gpu"][0], out["cpu"][0]), it
+        assert np.array_equal(out["gpu"][1], out["cpu"][1]), it
+    ca.set_mode("cpu")
+
+
+def test_mean_value_count_is_checked(db):
+    # the reference's DataTransformer rejects a mean_value count that is
+    # neither 1 nor the channel count; one value broadcasts
+    ca.set_mode("cpu")
+    with pytest.raises(Exception) as e:
+        net_from_text(data_net(db, mean=[10, 20]))
+    msg = str(e.value)
+    assert "mean_value" in msg and "'data'" in msg
+    assert "2 mean_value" in msg and f"{C} channels" in msg
+    for mean in ([10], [10, 20, 30]):
+        net = net_from_text(data_net(db, batch=2, mean=mean))
+        net.forward()
+        data = np.asarray(net.blob("data")).reshape(2, C, H, W)
+        m = np.resize(np.array(mean, np.float32), C).reshape(C, 1, 1)
+        assert np.array_equal(data[0], expected_image(0) - m)
+
+
 @pytest.mark.gpu
 def test_lmdb_gpu_training(db):
     # short GPU training run off the LMDB feed (prefetch worker + device
@@ -342,17 +426,10 @@ def test_mean_file_binaryproto(db, tmp_path):
     # transform_param.mean_file: a BlobProto (binaryproto) full-size mean,
     # subtracted in SOURCE coordinates — encoded here independently
     # (field 7 shape{dim}, field 5 packed float data)
-    from make_lmdb import varint
     rng = np.random.default_rng(77)
     mean = rng.uniform(0, 255, (C, H, W)).astype(np.float32)
-    shape_msg = b""
-    for d in (C, H, W):
-        shape_msg += b"\x08" + varint(d)
-    blob = b"\x3a" + varint(len(shape_msg)) + shape_msg  # field 7 (shape)
-    data = mean.ravel().tobytes()
-    blob += b"\x2a" + varint(len(data)) + data           # field 5 packed
     mf = tmp_path / "mean.binaryproto"
-    mf.write_bytes(blob)
+    binaryproto_mean(mf, mean)
     ca.set_mode("cpu")
     net = net_from_text(f"""name: "t"
 layer {{

@@ -46,8 +46,8 @@ int main(int argc, char** argv) {
   const size_t pbytes = std::max<size_t>(
       sizeof(double) * gpu::loss_partials(n), 2 * sizeof(double) * C * nb);
   HIP_CHECK(hipMalloc((void**)&partials, pbytes));
-  gpu::fill_uniform(s, n, 1, 0, -3.f, 3.f, a);  // logits / activations
-  gpu::fill_uniform(s, n, 2, 0, 0.f, 1.f, b);   // targets / top data
+  gpu::fill_uniform(s, n, 1, -3.f, 3.f, a);  // logits / activations
+  gpu::fill_uniform(s, n, 2, 0.f, 1.f, b);   // targets / top data
   const double fb = (double)n * sizeof(float);
   std::vector<Variant> v = {
       {"k_relu_fwd", 2 * fb,
