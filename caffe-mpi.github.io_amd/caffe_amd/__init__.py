@@ -273,7 +273,11 @@ def kernel_trace_read():
     nsrc; contrastive_fwd | contrastive_bwd with var (row_thread | row_wave),
     N, C, blocks.  With clip_gradients set: grad_sumsq (a bucket's sum of
     squares) with lo, hi, blocks, passes; clip_final with partials; and the
-    sgd_seg / solver_seg records carry clip=1."""
+    sgd_seg / solver_seg records carry clip=1.  A depthwise Convolution
+    records dwconv_fwd | dwconv_bwd_data with var (k3s1 | k3s2 | generic,
+    then _plane | _tile), planes (per block), tiles_y, tiles_x, blocks, and
+    dwconv_bwd_weight with var (k3 | generic), slices (batch slices), bias
+    (db summed in the same pass), blocks."""
     return _trace_records(_lib.caffe_kernel_trace_read)
 
 

@@ -39,7 +39,7 @@ enum KOp {
   kBnBwdStats, kLrnFwd, kLrnBwd, kSoftmaxFwd, kSgdSeg, kSolverSeg,
   kSigmoidFwd, kSigmoidBwd, kSigmoidCeFwd, kSigmoidCeBwd, kEuclidFwd,
   kEuclidBwd, kSharedDiffSum, kContrastiveFwd, kContrastiveBwd, kGradSumsq,
-  kClipFinal
+  kClipFinal, kDwFwd, kDwBwdData, kDwBwdWeight
 };
 enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
             kVarScalar, kVarRing5, kVarRowThread, kVarRowWave };
@@ -64,6 +64,10 @@ static inline void ktrace(int op, int var = kVarNone, long a = 0, long b = 0,
   if (g_ktrace_on.load(std::memory_order_relaxed))
     ktrace_push(op, var, a, b, c, d);
 }
+void kernel_trace_dwconv(int which, int var, long a, long b, long c,
+                         long d) {
+  ktrace(kDwFwd + which, var, a, b, c, d);
+}
 void kernel_trace(bool enable) {
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   if (enable) {
@@ -80,7 +84,12 @@ long kernel_trace_read(char* buf, long cap) {
       "softmax_fwd",  "sgd_seg",      "solver_seg",   "sigmoid_fwd",
       "sigmoid_bwd",  "sigmoid_ce_fwd", "sigmoid_ce_bwd", "euclid_fwd",
       "euclid_bwd",   "shared_diff_sum", "contrastive_fwd",
-      "contrastive_bwd", "grad_sumsq",  "clip_final"};
+      "contrastive_bwd", "grad_sumsq",  "clip_final", "dwconv_fwd",
+      "dwconv_bwd_data", "dwconv_bwd_weight"};
+  // the depthwise ops keep kind * 2 + tiled in the var byte
+  static const char* const dwvar[] = {"k3s1_plane", "k3s1_tile",
+                                      "k3s2_plane", "k3s2_tile",
+                                      "generic_plane", "generic_tile"};
   // solver_seg keeps rule * 2 + l1 in the var byte
   static const char* const rule[] = {"sgd",     "nesterov", "adagrad",
                                      "rmsprop", "adadelta", "adam"};
@@ -156,6 +165,18 @@ long kernel_trace_read(char* buf, long cap) {
       case kContrastiveBwd:
         n = snprintf(line, sizeof(line), "op=%s var=%s N=%ld C=%ld blocks=%ld\n",
                      op[r.op], var[r.var], r.a, r.b, r.c);
+        break;
+      case kDwFwd:
+      case kDwBwdData:
+        n = snprintf(line, sizeof(line),
+                     "op=%s var=%s planes=%ld tiles_y=%ld tiles_x=%ld "
+                     "blocks=%ld\n",
+                     op[r.op], dwvar[r.var], r.a, r.b, r.c, r.d);
+        break;
+      case kDwBwdWeight:
+        n = snprintf(line, sizeof(line),
+                     "op=%s var=%s slices=%ld bias=%ld blocks=%ld\n", op[r.op],
+                     r.var ? "generic" : "k3", r.a, r.b, r.d);
         break;
       default:  // sgd_seg; d as for solver_seg
         n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld%s\n",

@@ -146,6 +146,7 @@ struct Workspace {
     kBiasPart,  // bias_grad(): per-slice double partials
     kLossPart,  // sigmoid_ce_fwd() / euclid_fwd() / contrastive_fwd():
                 // per-block double partials
+    kDwPart,    // dwconv_bwd_weight(): per-(channel, slice) double partials
     kNumSlots
   };
   void* get(Slot slot, size_t bytes);  // device (GPU mode) / host (CPU mode)
@@ -217,8 +218,10 @@ class ConvolutionLayer : public Layer {
   // GPU plan, decided once per Reshape by plan_gpu() (layers_gpu.cpp, with
   // the policy): how forward and wgrad read x, and how dgrad is done.
   // Forward_gpu and Backward_gpu switch on it and never re-derive it.
-  enum XOperand { kChanView, kIm2colView, kExplicitCol };
-  enum Dgrad { kTnScatter, kFlipConv, kStridedScatter, kCol2im };
+  // kDepthwise / kDwGather (always together): the direct depthwise kernels,
+  // no GEMM at all.
+  enum XOperand { kChanView, kIm2colView, kExplicitCol, kDepthwise };
+  enum Dgrad { kTnScatter, kFlipConv, kStridedScatter, kCol2im, kDwGather };
   XOperand xop_ = kExplicitCol;
   Dgrad dgrad_ = kCol2im;
   void plan_gpu();

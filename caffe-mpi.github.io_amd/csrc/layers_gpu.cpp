@@ -35,7 +35,33 @@ using gpu::GemmView;
 // sampled input pixels).  Dilation stays explicit.  The strided scatter
 // never meets the im2col view — a strided view needs kh > 1, the scatter
 // kh == 1 — so it is tested on its own, after the stride-1 view.
+//
+// DEPTHWISE (one input channel per group, any channel multiplier, stride,
+// pad and dilation) leaves the GEMM family: the per-group loop would run
+// `group` GEMMs of M = multiplier, K = kh*kw per pass, all launch latency.
+// It takes the direct kernels of kernels/depthwise.hip when group >= 8 and
+// kh*kw <= 49 (and the dilated window fits the kernels' LDS tile, which any
+// window that fits a real image does).  The group >= 8 bound is a policy
+// constant and has NOT been measured: it is chosen so that no shape in the
+// existing suites changes route (they use group <= 4: the geometry sweep
+// can draw C = 4 / group 4, the torch cross-check C = 2 / group 2).
+// CAFFE_DEPTHWISE=0 forces the per-group loop, for measuring one against
+// the other.
+static gpu::DwConv dw_geom(const ConvolutionLayer& l) {
+  return {l.N_,  l.C_,  l.Cout_ / l.C_, l.H_,  l.W_,  l.OH_, l.OW_, l.kh_,
+          l.kw_, l.sh_, l.sw_,          l.ph_, l.pw_, l.dh_, l.dw_};
+}
 void ConvolutionLayer::plan_gpu() {
+  static const bool depthwise_ok = [] {
+    const char* e = getenv("CAFFE_DEPTHWISE");
+    return e ? atoi(e) != 0 : true;
+  }();
+  if (depthwise_ok && C_ / group_ == 1 && group_ >= 8 && kh_ * kw_ <= 49 &&
+      gpu::dwconv_supported(dw_geom(*this))) {
+    xop_ = kDepthwise;
+    dgrad_ = kDwGather;
+    return;
+  }
   static const int min_ow = [] {
     const char* e = getenv("CAFFE_IMPLICIT_MIN_OW");
     return e ? atoi(e) : 24;
@@ -97,6 +123,10 @@ void ConvolutionLayer::Forward_gpu(const std::vector<Blob*>& bottom,
   const float* w = blobs_[0]->gpu_data();
   const float* bias = bias_ ? blobs_[1]->gpu_data() : nullptr;
   float* y = top[0]->mutable_gpu_data();
+  if (xop_ == kDepthwise) {
+    gpu::dwconv_fwd(E.stream, dw_geom(*this), x, w, bias, fuse_relu_, y);
+    return;
+  }
 
   // B is x through the plan's view, or the col buffer (cached for backward)
   const bool col = xop_ == kExplicitCol;
@@ -129,6 +159,15 @@ void ConvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
   const float* w = blobs_[0]->gpu_data();
   const float* dy = top[0]->gpu_diff();
   GemmView dyv{Spad_, S_, Cout_};  // dY[N][Cout][S] as [Cout][N*Spad]
+
+  if (xop_ == kDepthwise) {  // wgrad's pass over dy also sums db
+    const gpu::DwConv g = dw_geom(*this);
+    gpu::dwconv_bwd_weight(E.stream, g, x, dy, blobs_[0]->mutable_gpu_diff(),
+                           bias_ ? blobs_[1]->mutable_gpu_diff() : nullptr);
+    if (prop_down[0])
+      gpu::dwconv_bwd_data(E.stream, g, dy, w, bottom[0]->mutable_gpu_diff());
+    return;
+  }
 
   if (bias_)
     gpu::bias_grad(E.stream, dy, N_, Cout_, S_,
@@ -208,6 +247,8 @@ void ConvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
                           sh_, sw_, dh_, dw_, OH_, OW_, Spad_, dx);
       break;
     }
+    case kDwGather:  // returned above
+      break;
   }
 }
 

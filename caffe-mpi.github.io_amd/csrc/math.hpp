@@ -298,8 +298,36 @@ void gemm_trace_readers(long* cursor, long* wide64);
 //   op=clip_final partials=<doubles summed>
 // With clip_gradients set, sgd_seg and solver_seg records end in " clip=1"
 // (the launch read the factor); without it their text is as above.
+//   op=dwconv_fwd|dwconv_bwd_data var=k3s1_plane|k3s1_tile|k3s2_plane|
+//       k3s2_tile|generic_plane|generic_tile planes=<(n, c) planes per block>
+//       tiles_y=<tiles per plane> tiles_x=<likewise> blocks=<grid>
+//   op=dwconv_bwd_weight var=k3|generic slices=<batch slices> bias=<0|1: db
+//       accumulated in the same pass> blocks=<first-stage grid>
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
+// The depthwise wrappers (kernels/depthwise.hip) record into the same log:
+// which = 0 forward, 1 dgrad, 2 wgrad; var = kind * 2 + (tiled ? 1 : 0) with
+// kind 0 k3s1, 1 k3s2, 2 generic (wgrad: 0 k3, 1 generic); a..d as printed.
+void kernel_trace_dwconv(int which, int var, long a, long b, long c, long d);
+
+// Depthwise convolution (Convolution with group == C): x[N][C][H][W],
+// w[C*mult][1][kh][kw], y[N][C*mult][OH][OW]; output channel c*mult + j
+// reads input channel c.  Direct kernels, no col buffer (depthwise.hip).
+struct DwConv {
+  int N, C, mult, H, W, OH, OW, kh, kw, sh, sw, ph, pw, dh, dw;
+};
+// false when even the smallest tile's window (kernel extent with dilation)
+// does not fit the LDS tile; the conv plan then keeps the GEMM route
+bool dwconv_supported(const DwConv& g);
+// y = conv(x, w) (+ bias) (then ReLU)
+void dwconv_fwd(hipStream_t s, const DwConv& g, const float* x,
+                const float* w, const float* bias, bool relu, float* y);
+// dx overwritten, every element once (gather form)
+void dwconv_bwd_data(hipStream_t s, const DwConv& g, const float* dy,
+                     const float* w, float* dx);
+// dw (and db = Σ dy when db is given) overwritten; two-stage, deterministic
+void dwconv_bwd_weight(hipStream_t s, const DwConv& g, const float* x,
+                       const float* dy, float* dw, float* db);
 
 // db[c] = Σ_n Σ_s dy[n][c][s] (deterministic)
 void bias_grad(hipStream_t s, const float* dy, int N, int C, long S,

@@ -226,7 +226,16 @@ int caffe_gemm_trace_readers(long* cursor, long* wide64);
  * ContrastiveLoss kernels record
  * "op=contrastive_fwd var=row_thread N=64 C=2 blocks=1" and
  * "op=contrastive_bwd var=row_wave N=3 C=257 blocks=1" (one thread or one
- * wave per row). */
+ * wave per row).  A depthwise Convolution (group == input channels, the
+ * direct kernels in place of the per-group GEMM loop) records
+ * "op=dwconv_fwd var=k3s1_plane planes=4 tiles_y=1 tiles_x=1 blocks=20",
+ * "op=dwconv_bwd_data var=k3s2_tile planes=1 tiles_y=4 tiles_x=3 blocks=192"
+ * (var: k3s1 | k3s2 | generic kernel, then _plane = several whole (n, c)
+ * planes per block or _tile = 2-D tiles of one plane; planes per block, tile
+ * grid per plane, launch grid) and
+ * "op=dwconv_bwd_weight var=k3 slices=2 bias=1 blocks=32" (var k3 | generic,
+ * batch slices of the first stage, whether the pass also summed the bias
+ * gradient, first-stage grid). */
 int caffe_kernel_trace(int enable);
 int caffe_kernel_trace_read(char* buf, int cap);
 /* The graph fusions planned for a net at build time, same buffer contract
