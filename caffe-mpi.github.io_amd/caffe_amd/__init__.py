@@ -89,6 +89,7 @@ _lib.caffe_gemm_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_kernel_trace_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_net_fusions.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_net_diff_sharing.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
+_lib.caffe_net_join_backward.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_net_param_sharing.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int]
 _lib.caffe_fastdiv_selftest.argtypes = [ctypes.c_uint, ctypes.c_uint]
 _lib.caffe_fastdiv_selftest.restype = ctypes.c_long
@@ -353,6 +354,14 @@ class Net:
         where every such bottom is copied."""
         return [tuple(f) for f in
                 self._plan_lines(_lib.caffe_net_diff_sharing)]
+
+    def join_backward(self):
+        """The residual-join backwards planned at build time, in layer
+        order: one (split layer, relu layer) per two-top Split directly
+        after a ReLU whose backward the Split's GPU backward absorbs (see
+        caffe_amd.h).  The same in CPU mode, where nothing is fused."""
+        return [tuple(f) for f in
+                self._plan_lines(_lib.caffe_net_join_backward)]
 
     def param_sharing(self):
         """The shared params planned at build time, in layer order: one

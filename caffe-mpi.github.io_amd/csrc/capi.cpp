@@ -639,6 +639,16 @@ int caffe_net_diff_sharing(caffe_net_t n, char* buf, int cap) {
   API_CATCH
 }
 
+int caffe_net_join_backward(caffe_net_t n, char* buf, int cap) {
+  API_TRY
+  auto& layers = N(n)->layers();
+  std::vector<std::string> lines;
+  for (auto& j : N(n)->join_backward())
+    lines.push_back(layers[j.split]->name() + " " + layers[j.relu]->name());
+  return plan_lines(lines, buf, cap);
+  API_CATCH
+}
+
 int caffe_net_param_sharing(caffe_net_t n, char* buf, int cap) {
   API_TRY
   auto& layers = N(n)->layers();

@@ -767,32 +767,6 @@ void bn_fwd_stats(hipStream_t s, const float* x, int N, int C, long S,
   ktrace_bn(kBnFwdStats, kVarScalar, N, nb, S);
 }
 
-__global__ void k_bn_fwd_finalize(const double2* __restrict__ partials,
-                                  int nb, int C, long NS, float eps,
-                                  float* __restrict__ mean,
-                                  float* __restrict__ var,
-                                  float* __restrict__ inv_std) {
-  GRID_STRIDE(c, (long)C) {
-    double s1 = 0, s2 = 0;
-    for (int b = 0; b < nb; ++b) {
-      s1 += partials[c * nb + b].x;
-      s2 += partials[c * nb + b].y;
-    }
-    const double m = s1 / NS;
-    const double v = s2 / NS - m * m;  // E[x^2]-m^2 in double ≈ E[(x-m)^2]
-    mean[c] = (float)m;
-    var[c] = (float)v;
-    inv_std[c] = (float)(1.0 / sqrt(v + (double)eps));
-  }
-}
-void bn_fwd_finalize(hipStream_t s, const void* partials, int nb, int C,
-                     long NS, float eps, float* mean, float* var,
-                     float* inv_std) {
-  hipLaunchKernelGGL(k_bn_fwd_finalize, dim3(1), dim3(TPB), 0, s,
-                     (const double2*)partials, nb, C, NS, eps, mean, var,
-                     inv_std);
-}
-
 // The norm / apply kernels walk the tensor as flat float4 packs; per pack
 // ONE division recovers the channel.  A pack that straddles a channel
 // boundary (whole == false) takes the channel per element, from bn_chan.
@@ -868,27 +842,6 @@ void bn_fwd_norm(hipStream_t s, const float* x, const float* mean,
   hipLaunchKernelGGL(k_bn_fwd_norm, dim3(nblocks(n4, 4)), dim3(TPB), 0, s,
                      (const f4*)x, mean, inv_std, scale, bias, sb, C,
                      (int)S, fuse_relu, n4, (const f4*)add, (f4*)y);
-}
-
-__global__ void k_bn_moving_avg(const float* __restrict__ mean,
-                                const float* __restrict__ var, int C,
-                                float maf, int copy_only,
-                                float* __restrict__ gmean,
-                                float* __restrict__ gvar) {
-  GRID_STRIDE(c, (long)C) {
-    if (copy_only) {
-      gmean[c] = mean[c];
-      gvar[c] = var[c];
-    } else {  // batch_norm_layer.cpp:200-207
-      gmean[c] = (1.f - maf) * mean[c] + maf * gmean[c];
-      gvar[c] = (1.f - maf) * var[c] + maf * gvar[c];
-    }
-  }
-}
-void bn_moving_avg(hipStream_t s, const float* mean, const float* var, int C,
-                   float maf, int copy_only, float* gmean, float* gvar) {
-  hipLaunchKernelGGL(k_bn_moving_avg, dim3(1), dim3(TPB), 0, s, mean, var,
-                     C, maf, copy_only, gmean, gvar);
 }
 
 __global__ void k_bn_fwd_test(const float* __restrict__ x,

@@ -376,6 +376,14 @@ class ReLULayer : public Layer {
   // materialized: backward masks by the TOP's sign — identical for
   // slope 0 (top > 0 <=> bottom > 0)
   bool bwd_from_top_ = false;
+  // GPU: the two-top Split directly after this layer applies the mask while
+  // it sums its tops' gradients and writes this layer's bottom diff; the
+  // backward here launches nothing (set from Net::plan_join_backward)
+  bool bwd_in_split_ = false;
+  float slope() const {
+    auto rp = param_->sub("relu_param");
+    return rp ? (float)rp->num("negative_slope", 0) : 0.f;
+  }
   void Reshape(const std::vector<Blob*>& b,
                const std::vector<Blob*>& t) override {
     if (b[0] != t[0]) t[0]->ReshapeLike(*b[0]);
@@ -509,6 +517,13 @@ class SplitLayer : public Layer {
   // GPU, one top: the bottom's diff shares the top's diff memory and
   // backward launches nothing (set from Net::plan_diff_sharing)
   bool alias_diff_ = false;
+  // GPU, two tops directly after a ReLU that nothing else consumes (set from
+  // Net::plan_join_backward): backward sums the tops' gradients, masks the
+  // sum as that ReLU's backward would (by the sign of join_ref_'s data) and
+  // writes the ReLU's bottom diff, all in one pass
+  Blob* join_ref_ = nullptr;
+  Blob* join_dx_ = nullptr;
+  float join_slope_ = 0.f;
 };
 
 class SoftmaxLayer : public Layer {

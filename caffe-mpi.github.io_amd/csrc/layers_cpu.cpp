@@ -946,6 +946,12 @@ void SplitLayer::Backward_gpu(const std::vector<Blob*>& top,
   if (!prop_down[0] || alias_diff_) return;
   Engine& E = Engine::get();
   const long n = bottom[0]->count();
+  if (join_dx_) {  // the sum and the ReLU backward below it in one pass
+    gpu::add_relu_bwd(E.stream, n, top[0]->gpu_diff(), top[1]->gpu_diff(),
+                      join_ref_->gpu_data(), join_slope_,
+                      join_dx_->mutable_gpu_diff());
+    return;
+  }
   float* dx = bottom[0]->mutable_gpu_diff();
   if (top.size() == 2) {  // single fused pass for the common fan-out of 2
     gpu::add3(E.stream, n, top[0]->gpu_diff(), top[1]->gpu_diff(), dx);

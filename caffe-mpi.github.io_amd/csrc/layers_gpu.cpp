@@ -338,9 +338,13 @@ void BatchNormLayer::Forward_gpu(const std::vector<Blob*>& bottom,
   partials_.Reshape({(int)(C_ * nb * 4)});  // double2 = 4 floats
   void* parts = partials_.mutable_gpu_data();
   gpu::bn_fwd_stats(E.stream, x, N, C_, S, nb, parts);
-  gpu::bn_fwd_finalize(E.stream, parts, nb, C_, (long)N * S, eps_,
-                       mean_.mutable_gpu_data(), var_.mutable_gpu_data(),
-                       inv_std_.mutable_gpu_data());
+  // the finalize also advances the global statistics, which nothing else
+  // in the TRAIN forward reads or writes
+  gpu::bn_fwd_finalize(E.stream, parts, nb, C_, (long)N * S, eps_, maf_,
+                       iter_ <= 1 ? 1 : 0, mean_.mutable_gpu_data(),
+                       var_.mutable_gpu_data(), inv_std_.mutable_gpu_data(),
+                       blobs_[0]->mutable_gpu_data(),
+                       blobs_[1]->mutable_gpu_data());
   const float* add = nullptr;
   int frelu = fuse_relu_;
   if (fuse_add_out_) {  // fused residual add: write the sum's top directly
@@ -350,9 +354,6 @@ void BatchNormLayer::Forward_gpu(const std::vector<Blob*>& bottom,
   }
   gpu::bn_fwd_norm(E.stream, x, mean_.gpu_data(), inv_std_.gpu_data(), sc,
                    bi, scale_bias_, N, C_, S, y, frelu, add);
-  gpu::bn_moving_avg(E.stream, mean_.gpu_data(), var_.gpu_data(), C_, maf_,
-                     iter_ <= 1 ? 1 : 0, blobs_[0]->mutable_gpu_data(),
-                     blobs_[1]->mutable_gpu_data());
   ++iter_;
 }
 
@@ -484,8 +485,8 @@ void ReLULayer::Backward_gpu(const std::vector<Blob*>& top,
                              const std::vector<Blob*>& bottom) {
   if (!prop_down[0]) return;
   if (fused_away_ && bwd_fused_) return;  // absorbed into BN backward
-  auto rp = param_->sub("relu_param");
-  const float slope = rp ? (float)rp->num("negative_slope", 0) : 0.f;
+  if (bwd_in_split_) return;  // the Split above already wrote our bottom diff
+  const float slope = this->slope();
   // bwd_from_top_: the pre-activation was never materialized (fused
   // producer wrote post-ReLU into our top); for slope 0 the top's sign
   // is the same mask

@@ -367,20 +367,23 @@ void pool_ave_bwd(hipStream_t s, const float* dy, int N, int C, int H, int W,
                   int OW, float* dx);
 
 // Fused BatchNorm (replaces the reference's ~10-launch GEMV chain,
-// batch_norm_layer.hpp:96-120, with 3 kernels fwd / 3 bwd).
+// batch_norm_layer.hpp:96-120, with 3 kernels fwd / 3 bwd; the forward
+// finalize also advances the moving averages).
 // partials: double2[nb*C] workspace. mean/var/inv_std: float[C] device.
 int bn_blocks_per_channel(int N, int C);
 void bn_fwd_stats(hipStream_t s, const float* x, int N, int C, long S,
                   int nb, void* partials);
+// mean / var / inv_std from the partials, then the moving averages of the
+// global statistics from them: g = (1 - maf) * batch + maf * g, or a plain
+// copy of the batch value when copy_only (kernels/join_bn.hip)
 void bn_fwd_finalize(hipStream_t s, const void* partials, int nb, int C,
-                     long NS, float eps, float* mean, float* var,
-                     float* inv_std);
+                     long NS, float eps, float maf, int copy_only,
+                     float* mean, float* var, float* inv_std, float* gmean,
+                     float* gvar);
 void bn_fwd_norm(hipStream_t s, const float* x, const float* mean,
                  const float* inv_std, const float* scale, const float* bias,
                  int scale_bias, int N, int C, long S, float* y,
                  int fuse_relu = 0, const float* add = nullptr);
-void bn_moving_avg(hipStream_t s, const float* mean, const float* var, int C,
-                   float maf, int copy_only, float* gmean, float* gvar);
 void bn_fwd_test(hipStream_t s, const float* x, const float* gmean,
                  const float* gvar, const float* scale, const float* bias,
                  int scale_bias, int N, int C, long S, float eps, float* y);
@@ -463,6 +466,11 @@ void copy(hipStream_t s, long n, const float* x, float* y);
 void set_const(hipStream_t s, long n, float v, float* y);
 void add3(hipStream_t s, long n, const float* a, const float* b, float* y,
           int fuse_relu = 0);
+// dx = (a + b) * (ref > 0 ? 1 : slope): add3 then relu_bwd in one pass, the
+// same two fp32 operations per element; dx may be a or b
+// (kernels/join_bn.hip)
+void add_relu_bwd(hipStream_t s, long n, const float* a, const float* b,
+                  const float* ref, float slope, float* dx);
 // y[n0..] accumulate: y += x
 void acc(hipStream_t s, long n, const float* x, float* y);
 

@@ -138,9 +138,14 @@ void Net::init(const PMsgPtr& msg, int batch_override) {
   collect_params();
   fusions_ = plan_fusions();
   diff_sharing_ = plan_diff_sharing();
+  join_backward_ = plan_join_backward();
   if (Engine::get().mode == Mode::GPU) {
     apply_fusions();
     apply_diff_sharing();
+    // CAFFE_JOIN_BWD=0 keeps the Split and ReLU backwards apart, for
+    // measuring and testing one against the other
+    const char* jb = getenv("CAFFE_JOIN_BWD");
+    if (!jb || atoi(jb) != 0) apply_join_backward();
     setup_arena();
   }
   setup_shared_sums();
@@ -537,6 +542,47 @@ void Net::apply_diff_sharing() {
       el->alias_diff_[s->bottom] = true;
     else
       static_cast<SplitLayer*>(l)->alias_diff_ = true;
+  }
+}
+
+// ---------------------------------------------------- join-backward plan
+std::vector<Net::JoinBackward> Net::plan_join_backward() const {
+  std::vector<JoinBackward> plan;
+  for (int i = 1; i < (int)layers_.size(); ++i) {
+    if (!dynamic_cast<SplitLayer*>(layers_[i].get())) continue;
+    if (tops_[i].size() != 2 || !prop_down_[i][0]) continue;
+    const int r = i - 1;
+    if (!dynamic_cast<ReLULayer*>(layers_[r].get())) continue;
+    if (bottoms_[r].size() != 1 || !prop_down_[r][0]) continue;
+    const Blob* blob = bottoms_[i][0];
+    if (!fed_by_previous(i, blob)) continue;
+    // a ReLU whose mask a BN applies in its own backward launches nothing
+    bool absorbed = false;
+    for (auto& f : fusions_)
+      absorbed = absorbed || (f.kind == Fusion::BN_RELU && f.absorbed[0] == r);
+    if (absorbed) continue;
+    // the Split is the blob's one reader from here on (an in-place ReLU
+    // reads the same blob, below the Split)
+    int readers = 0;
+    for (int k = i; k < (int)layers_.size(); ++k)
+      for (auto* b : bottoms_[k]) readers += b == blob;
+    if (readers == 1) plan.push_back({i, r});
+  }
+  return plan;
+}
+
+// after apply_fusions(): what the ReLU's backward reads depends on
+// bwd_from_top_
+void Net::apply_join_backward() {
+  for (auto& j : join_backward_) {
+    auto* split = static_cast<SplitLayer*>(layers_[j.split].get());
+    auto* relu = static_cast<ReLULayer*>(layers_[j.relu].get());
+    split->join_ref_ = in_place(j.relu) || relu->bwd_from_top_
+                           ? tops_[j.relu][0]
+                           : bottoms_[j.relu][0];
+    split->join_dx_ = bottoms_[j.relu][0];
+    split->join_slope_ = relu->slope();
+    relu->bwd_in_split_ = true;
   }
 }
 

@@ -149,6 +149,23 @@ class Net {
   // in layer order, then bottom order
   const std::vector<DiffShare>& diff_sharing() const { return diff_sharing_; }
 
+  // A Split with two propagating tops directly after a ReLU (in place or
+  // not, any slope) that runs its own backward and that nothing but the
+  // Split consumes: the Split's backward sums its tops' gradients, applies
+  // the ReLU's mask and writes the ReLU's bottom diff in one pass, and the
+  // ReLU's backward launches nothing (the residual join of a ResNet block).
+  // The two backwards are adjacent, so no layer runs between them and the
+  // diff-sharing plan stands as it is.  Planned from the built graph in both
+  // modes like the fusions; only GPU mode applies it, and CAFFE_JOIN_BWD=0
+  // (read at net build) leaves it unapplied.
+  struct JoinBackward {
+    int split, relu;  // layer indices, relu == split - 1
+  };
+  // in layer order
+  const std::vector<JoinBackward>& join_backward() const {
+    return join_backward_;
+  }
+
   // Named param blobs (reference Net::AppendParam, net.cpp:576-667): the
   // first blob of a name owns it, every later one is a sharer.  A sharer
   // uses the owner's data memory, is no learnable param, and keeps a diff
@@ -184,6 +201,8 @@ class Net {
   void apply_fusions();
   std::vector<DiffShare> plan_diff_sharing() const;
   void apply_diff_sharing();
+  std::vector<JoinBackward> plan_join_backward() const;
+  void apply_join_backward();
   void setup_arena();
   void setup_shared_sums();
 
@@ -225,6 +244,7 @@ class Net {
   std::vector<LParam> params_;
   std::vector<Fusion> fusions_;
   std::vector<DiffShare> diff_sharing_;
+  std::vector<JoinBackward> join_backward_;
   std::vector<ParamShare> param_sharing_;
   // What sum_shared_diffs runs for one owner layer: the sharers of its
   // learnable blobs in plan order and, in GPU mode, the layer's arena range

@@ -258,6 +258,18 @@ int caffe_net_fusions(caffe_net_t net, char* buf, int cap);
  * and gets one copy.  The same in CPU mode, where every such bottom is
  * copied. */
 int caffe_net_diff_sharing(caffe_net_t net, char* buf, int cap);
+/* The residual-join backwards planned at build time, read like the two
+ * plans above: one line "split relu" (layer names) per Split with two
+ * propagating tops that stands directly after a ReLU (in place or not, any
+ * negative_slope) which runs its own backward and whose top nothing but
+ * the Split reads, in layer order.  On the GPU that Split's backward sums
+ * its tops' gradients, applies the ReLU's mask and writes the ReLU's bottom
+ * gradient in one kernel, and the ReLU's backward launches nothing; the
+ * results are bit-identical to the two separate kernels.  With an
+ * out-of-place ReLU the gradient of the ReLU's top is then never written.
+ * CAFFE_JOIN_BWD=0 in the environment at net build leaves the plan
+ * unapplied.  The same list in CPU mode, where it is never applied. */
+int caffe_net_join_backward(caffe_net_t net, char* buf, int cap);
 /* The shared params of a net (reference Net::AppendParam, net.cpp:576-667),
  * planned at build time and read like the two plans above: one line
  * "layer blob_idx name owner_layer owner_blob_idx" per sharer, in layer
