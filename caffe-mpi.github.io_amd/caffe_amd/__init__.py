@@ -278,7 +278,12 @@ def kernel_trace_read():
     records dwconv_fwd | dwconv_bwd_data with var (k3s1 | k3s2 | generic,
     then _plane | _tile), planes (per block), tiles_y, tiles_x, blocks, and
     dwconv_bwd_weight with var (k3 | generic), slices (batch slices), bias
-    (db summed in the same pass), blocks."""
+    (db summed in the same pass), blocks.  A grouped Convolution with few
+    channels per group records gconv_fwd | gconv_bwd_data with var (as for
+    dwconv), cig, cog, chunks (LDS channel chunks per block), planes (images
+    per block), tiles_y, tiles_x, blocks, and gconv_bwd_weight with var
+    (k3s1 | k3s2 | generic), cig, cog, chunks (staged tiles per image), pairs
+    (output channels per thread), slices, bias, splits, blocks."""
     return _trace_records(_lib.caffe_kernel_trace_read)
 
 

@@ -39,12 +39,14 @@ enum KOp {
   kBnBwdStats, kLrnFwd, kLrnBwd, kSoftmaxFwd, kSgdSeg, kSolverSeg,
   kSigmoidFwd, kSigmoidBwd, kSigmoidCeFwd, kSigmoidCeBwd, kEuclidFwd,
   kEuclidBwd, kSharedDiffSum, kContrastiveFwd, kContrastiveBwd, kGradSumsq,
-  kClipFinal, kDwFwd, kDwBwdData, kDwBwdWeight
+  kClipFinal, kDwFwd, kDwBwdData, kDwBwdWeight, kGcFwd, kGcBwdData,
+  kGcBwdWeight
 };
 enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
             kVarScalar, kVarRing5, kVarRowThread, kVarRowWave };
 struct KernelRec {
   long a, b, c, d;  // per-op fields, see kernel_trace_read
+  long e, f, g, h;  // the grouped-conv ops alone
   unsigned char op, var;
 };
 constexpr size_t kKTraceCap = 4096;
@@ -57,7 +59,8 @@ static void ktrace_push(int op, int var, long a, long b, long c,
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   if (g_ktrace_log.size() < kKTraceCap)
     g_ktrace_log.push_back(
-        KernelRec{a, b, c, d, (unsigned char)op, (unsigned char)var});
+        KernelRec{a, b, c, d, 0, 0, 0, 0, (unsigned char)op,
+                  (unsigned char)var});
 }
 static inline void ktrace(int op, int var = kVarNone, long a = 0, long b = 0,
                           long c = 0, long d = 0) {
@@ -67,6 +70,14 @@ static inline void ktrace(int op, int var = kVarNone, long a = 0, long b = 0,
 void kernel_trace_dwconv(int which, int var, long a, long b, long c,
                          long d) {
   ktrace(kDwFwd + which, var, a, b, c, d);
+}
+void kernel_trace_gconv(int which, int var, const long (&f)[8]) {
+  if (!g_ktrace_on.load(std::memory_order_relaxed)) return;
+  std::lock_guard<std::mutex> lk(g_ktrace_mu);
+  if (g_ktrace_log.size() < kKTraceCap)
+    g_ktrace_log.push_back(KernelRec{f[0], f[1], f[2], f[3], f[4], f[5], f[6],
+                                     f[7], (unsigned char)(kGcFwd + which),
+                                     (unsigned char)var});
 }
 void kernel_trace(bool enable) {
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
@@ -85,8 +96,9 @@ long kernel_trace_read(char* buf, long cap) {
       "sigmoid_bwd",  "sigmoid_ce_fwd", "sigmoid_ce_bwd", "euclid_fwd",
       "euclid_bwd",   "shared_diff_sum", "contrastive_fwd",
       "contrastive_bwd", "grad_sumsq",  "clip_final", "dwconv_fwd",
-      "dwconv_bwd_data", "dwconv_bwd_weight"};
-  // the depthwise ops keep kind * 2 + tiled in the var byte
+      "dwconv_bwd_data", "dwconv_bwd_weight", "gconv_fwd",
+      "gconv_bwd_data", "gconv_bwd_weight"};
+  // the depthwise and grouped ops keep kind * 2 + tiled in the var byte
   static const char* const dwvar[] = {"k3s1_plane", "k3s1_tile",
                                       "k3s2_plane", "k3s2_tile",
                                       "generic_plane", "generic_tile"};
@@ -101,7 +113,7 @@ long kernel_trace_read(char* buf, long cap) {
   long len = 0;
   if (cap > 0) buf[0] = 0;
   for (const KernelRec& r : g_ktrace_log) {
-    char line[160];
+    char line[200];
     int n = 0;
     switch (r.op) {
       case kPoolMaxFwd:
@@ -177,6 +189,21 @@ long kernel_trace_read(char* buf, long cap) {
         n = snprintf(line, sizeof(line),
                      "op=%s var=%s slices=%ld bias=%ld blocks=%ld\n", op[r.op],
                      r.var ? "generic" : "k3", r.a, r.b, r.d);
+        break;
+      case kGcFwd:
+      case kGcBwdData:
+        n = snprintf(line, sizeof(line),
+                     "op=%s var=%s cig=%ld cog=%ld chunks=%ld planes=%ld "
+                     "tiles_y=%ld tiles_x=%ld blocks=%ld\n",
+                     op[r.op], dwvar[r.var], r.a, r.b, r.c, r.d, r.e, r.f,
+                     r.h);
+        break;
+      case kGcBwdWeight:
+        n = snprintf(line, sizeof(line),
+                     "op=%s var=%s cig=%ld cog=%ld chunks=%ld pairs=%ld "
+                     "slices=%ld bias=%ld splits=%ld blocks=%ld\n",
+                     op[r.op], var[kVarK3S1 + r.var], r.a, r.b, r.c, r.d, r.e,
+                     r.f, r.g, r.h);
         break;
       default:  // sgd_seg; d as for solver_seg
         n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld%s\n",

@@ -147,6 +147,7 @@ struct Workspace {
     kLossPart,  // sigmoid_ce_fwd() / euclid_fwd() / contrastive_fwd():
                 // per-block double partials
     kDwPart,    // dwconv_bwd_weight(): per-(channel, slice) double partials
+    kGcPart,    // gconv_bwd_weight(): per-(group, slice) double partials
     kNumSlots
   };
   void* get(Slot slot, size_t bytes);  // device (GPU mode) / host (CPU mode)
@@ -219,9 +220,14 @@ class ConvolutionLayer : public Layer {
   // the policy): how forward and wgrad read x, and how dgrad is done.
   // Forward_gpu and Backward_gpu switch on it and never re-derive it.
   // kDepthwise / kDwGather (always together): the direct depthwise kernels,
-  // no GEMM at all.
-  enum XOperand { kChanView, kIm2colView, kExplicitCol, kDepthwise };
-  enum Dgrad { kTnScatter, kFlipConv, kStridedScatter, kCol2im, kDwGather };
+  // no GEMM at all.  kGrouped / kGcGather (always together): the direct
+  // kernels for few channels per group, likewise.
+  enum XOperand {
+    kChanView, kIm2colView, kExplicitCol, kDepthwise, kGrouped
+  };
+  enum Dgrad {
+    kTnScatter, kFlipConv, kStridedScatter, kCol2im, kDwGather, kGcGather
+  };
   XOperand xop_ = kExplicitCol;
   Dgrad dgrad_ = kCol2im;
   void plan_gpu();

@@ -47,9 +47,28 @@ using gpu::GemmView;
 // can draw C = 4 / group 4, the torch cross-check C = 2 / group 2).
 // CAFFE_DEPTHWISE=0 forces the per-group loop, for measuring one against
 // the other.
+//
+// GROUPED with few channels per group (ResNeXt / ShuffleNet class) is tested
+// right after: cig = C/group in 4..32, cog = Cout/group in 1..32, group >= 8,
+// kh*kw <= 49, any stride, pad and dilation, and tiles that fit the LDS
+// budget (gconv_supported).  It takes the direct kernels of
+// kernels/grouped_conv.hip: no gemm, im2col, col2im or weight flip, no col_.
+// group >= 8 and cig >= 4 are policy constants like depthwise's and have
+// NOT been measured below: they keep every shape of the existing suites on
+// its present route (the geometry sweep uses group <= 4, the GEMM route
+// tests group 2, and the depthwise boundary test's cig = 2 at group 8 must
+// stay on the loop).  The upper bounds of 32 are where the measured shapes
+// end (profiles/grouped_conv.txt).  CAFFE_GROUPED=0 forces
+// the per-group loop.
 static gpu::DwConv dw_geom(const ConvolutionLayer& l) {
   return {l.N_,  l.C_,  l.Cout_ / l.C_, l.H_,  l.W_,  l.OH_, l.OW_, l.kh_,
           l.kw_, l.sh_, l.sw_,          l.ph_, l.pw_, l.dh_, l.dw_};
+}
+static gpu::GConv gc_geom(const ConvolutionLayer& l) {
+  return {l.N_,  l.group_, l.C_ / l.group_, l.Cout_ / l.group_,
+          l.H_,  l.W_,     l.OH_,           l.OW_,
+          l.kh_, l.kw_,    l.sh_,           l.sw_,
+          l.ph_, l.pw_,    l.dh_,           l.dw_};
 }
 void ConvolutionLayer::plan_gpu() {
   static const bool depthwise_ok = [] {
@@ -60,6 +79,17 @@ void ConvolutionLayer::plan_gpu() {
       gpu::dwconv_supported(dw_geom(*this))) {
     xop_ = kDepthwise;
     dgrad_ = kDwGather;
+    return;
+  }
+  static const bool grouped_ok = [] {
+    const char* e = getenv("CAFFE_GROUPED");
+    return e ? atoi(e) != 0 : true;
+  }();
+  const int cig = C_ / group_, cog = Cout_ / group_;
+  if (grouped_ok && group_ >= 8 && cig >= 4 && cig <= 32 && cog >= 1 &&
+      cog <= 32 && kh_ * kw_ <= 49 && gpu::gconv_supported(gc_geom(*this))) {
+    xop_ = kGrouped;
+    dgrad_ = kGcGather;
     return;
   }
   static const int min_ow = [] {
@@ -127,6 +157,10 @@ void ConvolutionLayer::Forward_gpu(const std::vector<Blob*>& bottom,
     gpu::dwconv_fwd(E.stream, dw_geom(*this), x, w, bias, fuse_relu_, y);
     return;
   }
+  if (xop_ == kGrouped) {
+    gpu::gconv_fwd(E.stream, gc_geom(*this), x, w, bias, fuse_relu_, y);
+    return;
+  }
 
   // B is x through the plan's view, or the col buffer (cached for backward)
   const bool col = xop_ == kExplicitCol;
@@ -166,6 +200,14 @@ void ConvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
                            bias_ ? blobs_[1]->mutable_gpu_diff() : nullptr);
     if (prop_down[0])
       gpu::dwconv_bwd_data(E.stream, g, dy, w, bottom[0]->mutable_gpu_diff());
+    return;
+  }
+  if (xop_ == kGrouped) {  // likewise
+    const gpu::GConv g = gc_geom(*this);
+    gpu::gconv_bwd_weight(E.stream, g, x, dy, blobs_[0]->mutable_gpu_diff(),
+                          bias_ ? blobs_[1]->mutable_gpu_diff() : nullptr);
+    if (prop_down[0])
+      gpu::gconv_bwd_data(E.stream, g, dy, w, bottom[0]->mutable_gpu_diff());
     return;
   }
 
@@ -248,6 +290,7 @@ void ConvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
       break;
     }
     case kDwGather:  // returned above
+    case kGcGather:
       break;
   }
 }

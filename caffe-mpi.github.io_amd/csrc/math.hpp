@@ -303,6 +303,13 @@ void gemm_trace_readers(long* cursor, long* wide64);
 //       tiles_y=<tiles per plane> tiles_x=<likewise> blocks=<grid>
 //   op=dwconv_bwd_weight var=k3|generic slices=<batch slices> bias=<0|1: db
 //       accumulated in the same pass> blocks=<first-stage grid>
+//   op=gconv_fwd|gconv_bwd_data var=<as dwconv_fwd> cig=<C/group>
+//       cog=<Cout/group> chunks=<LDS channel chunks per block> planes=<images
+//       per block> tiles_y=<tiles per plane> tiles_x=<likewise> blocks=<grid>
+//   op=gconv_bwd_weight var=k3s1|k3s2|generic cig=.. cog=.. chunks=<staged
+//       tiles per image> pairs=<output channels per thread (3x3)>
+//       slices=<batch slices> bias=<0|1> splits=<threads sharing an owner's
+//       pixels> blocks=<first-stage grid>
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
 // The depthwise wrappers (kernels/depthwise.hip) record into the same log:
@@ -328,6 +335,31 @@ void dwconv_bwd_data(hipStream_t s, const DwConv& g, const float* dy,
 // dw (and db = Σ dy when db is given) overwritten; two-stage, deterministic
 void dwconv_bwd_weight(hipStream_t s, const DwConv& g, const float* x,
                        const float* dy, float* dw, float* db);
+
+// The grouped wrappers (kernels/grouped_conv.hip) likewise: which as above;
+// var = kind * 2 + tiled (wgrad: kind); f = the eight fields as printed.
+void kernel_trace_gconv(int which, int var, const long (&f)[8]);
+
+// Grouped convolution with few channels per group: x[N][G*cig][H][W],
+// w[G*cog][cig][kh][kw], y[N][G*cog][OH][OW]; group g maps input channels
+// g*cig.. to output channels g*cog...  Direct kernels, no col buffer
+// (grouped_conv.hip).
+struct GConv {
+  int N, G, cig, cog, H, W, OH, OW, kh, kw, sh, sw, ph, pw, dh, dw;
+};
+// false when the smallest forward, dgrad or wgrad tile does not fit the LDS
+// budget or a tensor has 2^31 elements or more; the conv plan then keeps the
+// GEMM route
+bool gconv_supported(const GConv& g);
+// y = conv(x, w) (+ bias) (then ReLU)
+void gconv_fwd(hipStream_t s, const GConv& g, const float* x, const float* w,
+               const float* bias, bool relu, float* y);
+// dx overwritten, every element once (gather form)
+void gconv_bwd_data(hipStream_t s, const GConv& g, const float* dy,
+                    const float* w, float* dx);
+// dw (and db = Σ dy when db is given) overwritten; two-stage, deterministic
+void gconv_bwd_weight(hipStream_t s, const GConv& g, const float* x,
+                      const float* dy, float* dw, float* db);
 
 // db[c] = Σ_n Σ_s dy[n][c][s] (deterministic)
 void bias_grad(hipStream_t s, const float* dy, int N, int C, long S,

@@ -235,7 +235,15 @@ int caffe_gemm_trace_readers(long* cursor, long* wide64);
  * grid per plane, launch grid) and
  * "op=dwconv_bwd_weight var=k3 slices=2 bias=1 blocks=32" (var k3 | generic,
  * batch slices of the first stage, whether the pass also summed the bias
- * gradient, first-stage grid). */
+ * gradient, first-stage grid).  A grouped Convolution with few channels
+ * per group (group >= 8, 4..32 in and 1..32 out per group) records
+ * "op=gconv_fwd var=k3s1_plane cig=4 cog=4 chunks=1 planes=2 tiles_y=1
+ * tiles_x=1 blocks=8", op=gconv_bwd_data likewise (chunks: LDS channel
+ * chunks per block; planes: images per block) and "op=gconv_bwd_weight
+ * var=k3s1 cig=4 cog=4 chunks=1 pairs=1 slices=1 bias=1 splits=16 blocks=8"
+ * (var k3s1 | k3s2 | generic; staged tiles per image, output channels per
+ * thread, batch slices, bias summed, threads sharing an owner's pixels,
+ * first-stage grid). */
 int caffe_kernel_trace(int enable);
 int caffe_kernel_trace_read(char* buf, int cap);
 /* The graph fusions planned for a net at build time, same buffer contract

@@ -2,6 +2,13 @@
 against the per-group GEMM loop (profiles/depthwise_conv.txt).
 
   python tools/depthwise_bench.py [--repeats 3] [--iters 20] [--pkg DIR ...]
+                                  [--group G]
+
+With --group G the shapes are the grouped 3x3 layers of ResNeXt-50 32x4d
+instead (C = Cout at G groups: the gconv kernels against the loop,
+profiles/grouped_conv.txt), "loop" also sets CAFFE_GROUPED=0, and each
+direct kernel class is reported with its GFLOP/s and GB/s on algorithmic
+flops and bytes.
 
 Every (shape, variant) pair runs in a process of its own, the variants
 alternating shape by shape and repeat by repeat: "direct" (the default
@@ -25,20 +32,23 @@ BATCH = 64
 # MobileNet-v1 depthwise layers: (C, H = W, stride), 3x3 pad 1
 SHAPES = [(32, 112, 1), (128, 56, 1), (128, 56, 2), (512, 14, 1),
           (512, 14, 2), (1024, 7, 1)]
+# ResNeXt-50 32x4d grouped layers, likewise
+GROUPED_SHAPES = [(128, 56, 1), (256, 56, 2), (256, 28, 1), (512, 28, 2),
+                  (512, 14, 1), (1024, 14, 2), (1024, 7, 1)]
 
 
-def net_text(C, H, s, force_backward):
+def net_text(C, H, s, force_backward, group):
     return f"""name: "dw"
 force_backward: {"true" if force_backward else "false"}
 layer {{ name: "input" type: "Input" top: "in0"
   input_param {{ shape {{ dim: {BATCH} dim: {C} dim: {H} dim: {H} }} }} }}
 layer {{ name: "conv" type: "Convolution" bottom: "in0" top: "out"
-  convolution_param {{ num_output: {C} group: {C} kernel_size: 3 stride: {s}
+  convolution_param {{ num_output: {C} group: {group or C} kernel_size: 3 stride: {s}
     pad: 1 weight_filler {{ type: "xavier" }} }} }}
 """
 
 
-def child(C, H, s, iters, pkg):
+def child(C, H, s, iters, pkg, group):
     sys.path.insert(0, pkg)
     import numpy as np
     import caffe_amd as ca
@@ -47,7 +57,7 @@ def child(C, H, s, iters, pkg):
 
     def build(force_backward):
         f = tempfile.NamedTemporaryFile("w", suffix=".prototxt", delete=False)
-        f.write(net_text(C, H, s, force_backward))
+        f.write(net_text(C, H, s, force_backward, group))
         f.close()
         net = ca.Net.from_file(f.name)
         net.set_blob("in0", rng.standard_normal(
@@ -68,8 +78,11 @@ def child(C, H, s, iters, pkg):
         ca.device_synchronize()
         ca.set_perf_timing(False)
         perf = ca.perf_snapshot()
+        rates.update({k: (v["flops"] / v["ns"], v["bytes"] / v["ns"])
+                      for k, v in perf.items() if v["ns"]})
         return {k: v["ns"] / iters / 1e3 for k, v in perf.items() if v["ns"]}
 
+    rates = {}  # kernel class -> (GFLOP/s, GB/s)
     full, wonly = build(True), build(False)
     for _ in range(3):  # warm-up of every launch the windows time
         full.forward(), full.backward(), wonly.backward()
@@ -91,6 +104,7 @@ def child(C, H, s, iters, pkg):
         key = f'{r["fam"]} ta={r["ta"]} tb={r["tb"]} {r["M"]}x{r["N"]}x{r["K"]}'
         counts[key] = counts.get(key, 0) + 1
     out["gemms"] = counts
+    out["rates"] = rates
     print(json.dumps(out))
 
 
@@ -99,26 +113,32 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--pkg", action="append", default=[])
+    ap.add_argument("--group", type=int, default=0)
     ap.add_argument("--child", nargs=4)
     args = ap.parse_args()
     if args.child:
         C, H, s = map(int, args.child[:3])
-        return child(C, H, s, args.iters, args.child[3])
+        return child(C, H, s, args.iters, args.child[3], args.group)
 
     here = os.path.join(REPO, "caffe-mpi.github.io_amd")
     variants = [("direct", here, "1"), ("loop", here, "0")]
     variants += [("pkg:" + p, os.path.abspath(p), "1") for p in args.pkg]
-    for C, H, s in SHAPES:
+    for C, H, s in GROUPED_SHAPES if args.group else SHAPES:
         runs = {name: [] for name, _, _ in variants}
         for _ in range(args.repeats):
             for name, pkg, flag in variants:
                 res = subprocess.run(
                     [sys.executable, __file__, "--iters", str(args.iters),
+                     "--group", str(args.group),
                      "--child", str(C), str(H), str(s), pkg],
-                    env=dict(os.environ, CAFFE_DEPTHWISE=flag), timeout=120,
+                    env=dict(os.environ, CAFFE_DEPTHWISE=flag,
+                             CAFFE_GROUPED=flag), timeout=120,
                     capture_output=True, text=True, check=True)
                 runs[name].append(json.loads(res.stdout.splitlines()[-1]))
-        print(f"== {C}@{H}x{H} 3x3 s{s} batch {BATCH}")
+        print(f"== {C}@{H}x{H} 3x3 s{s} batch {BATCH}"
+              + (f" group {args.group}" if args.group else ""))
+        for name, _, _ in variants[2:]:  # the loop is the other build's route
+            assert runs["loop"][0]["gemms"] == runs[name][0]["gemms"], name
         for name, rs in runs.items():
             def stat(f):
                 v = [f(r) for r in rs]
@@ -131,6 +151,13 @@ def main():
                   f"bwd {stat(lambda r: sum(r['bwd_us'].values()))}")
             print(f"{'':>8}  gemms {json.dumps(rs[0]['gemms'], sort_keys=True)}",
                   flush=True)
+            if args.group and name == "direct":
+                for k in sorted(rs[0]["rates"]):
+                    v = [r["rates"][k] for r in rs]
+                    print(f"{'':>8}  {k}: "
+                          f"{statistics.median(a for a, _ in v):8.0f} GFLOP/s "
+                          f"{statistics.median(b for _, b in v):7.0f} GB/s",
+                          flush=True)
 
 
 if __name__ == "__main__":
