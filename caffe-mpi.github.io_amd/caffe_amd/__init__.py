@@ -283,7 +283,10 @@ def kernel_trace_read():
     dwconv), cig, cog, chunks (LDS channel chunks per block), planes (images
     per block), tiles_y, tiles_x, blocks, and gconv_bwd_weight with var
     (k3s1 | k3s2 | generic), cig, cog, chunks (staged tiles per image), pairs
-    (output channels per thread), slices, bias, splits, blocks."""
+    (output channels per thread), slices, bias, splits, blocks.  A
+    Deconvolution forward at stride > 1 and dilation 1 records deconv_fwd
+    with var (mfma | direct), phases (sh * sw), chunks (input-channel chunks
+    per block), tiles_y, tiles_x, blocks."""
     return _trace_records(_lib.caffe_kernel_trace_read)
 
 

@@ -148,6 +148,7 @@ struct Workspace {
                 // per-block double partials
     kDwPart,    // dwconv_bwd_weight(): per-(channel, slice) double partials
     kGcPart,    // gconv_bwd_weight(): per-(group, slice) double partials
+    kDeconvW,   // deconv_fwd(): the weights re-laid phase-major
     kNumSlots
   };
   void* get(Slot slot, size_t bytes);  // device (GPU mode) / host (CPU mode)
@@ -233,6 +234,42 @@ class ConvolutionLayer : public Layer {
   void plan_gpu();
   DeviceBuf col_;  // kExplicitCol: cached col buffer [C*kh*kw][N*Spad]
                    // (forward fills, backward reuses — no im2col recompute)
+};
+
+// Transposed convolution (reference deconv_layer.cpp: base_conv_layer with
+// reverse_dimensions()).  Its passes are the passes of the conv that maps
+// the TOP [N][Cout][OH][OW] to the BOTTOM [N][C][H][W] with the same
+// kernel, stride, pad and dilation, swapped: forward is that conv's
+// backward-data, backward-data its forward, and the weight gradient its
+// wgrad with the two tensors exchanged.  The blob [C][Cout/group][kh][kw] is
+// that conv's weight as stored.  Not a ConvolutionLayer: the net's conv+ReLU
+// epilogue fusion must not see it.
+class DeconvolutionLayer : public Layer {
+ public:
+  using Layer::Layer;
+  void LayerSetUp(const std::vector<Blob*>&,
+                  const std::vector<Blob*>&) override;
+  void Reshape(const std::vector<Blob*>&, const std::vector<Blob*>&) override;
+  void Forward_cpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Forward_gpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Backward_cpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+
+  int Cout_ = 0, kh_ = 0, kw_ = 0, sh_ = 1, sw_ = 1, ph_ = 0, pw_ = 0,
+      dh_ = 1, dw_ = 1, group_ = 1;
+  bool bias_ = true;
+  int N_ = 0, C_ = 0, H_ = 0, W_ = 0, OH_ = 0, OW_ = 0;  // bottom, top
+  long S_ = 0, Spad_ = 0;  // H*W (the conv's output pixels), 16-padded
+  // GPU forward: the phase-split kernel of kernels/deconv.hip, or dcol =
+  // Wᵀ·x, col2im and a bias pass.  Decided once per Reshape.
+  bool phase_split_ = false;
+  void plan_gpu();
+  DeviceBuf col_;  // backward: im2col of the top gradient [Cout*kh*kw][N*Spad]
+  Blob zo_;        // fallback forward: the ones of the bias pass
 };
 
 class InnerProductLayer : public Layer {

@@ -108,6 +108,19 @@ void fill_blob(Blob& b, const PMsgPtr& filler, std::mt19937_64& rng) {
       std::normal_distribution<float> d(0.f, (float)std::sqrt(2.0 / fan));
       for (long i = 0; i < n; ++i) p[i] = d(rng);
     }
+  } else if (type == "bilinear") {
+    // filler.hpp BilinearFiller: every [kh][kw] plane is the interpolation
+    // kernel of an upsampling by f = ceil(kw / 2); deterministic, no RNG draw
+    CHECK_EQ_(b.num_axes(), 4) << "bilinear filler: blob must be 4-d";
+    CHECK_EQ_(b.height(), b.width())
+        << "bilinear filler: kernel must be square";
+    const int kw = b.width();
+    const int f = (kw + 1) / 2;
+    const float c = (2 * f - 1 - f % 2) / (2.f * f);
+    for (long i = 0; i < n; ++i) {
+      const float x = (float)(i % kw), y = (float)((i / kw) % kw);
+      p[i] = (1 - std::fabs(x / f - c)) * (1 - std::fabs(y / f - c));
+    }
   } else {
     CAMD_FATAL << "unsupported filler type: " << type;
   }
@@ -144,25 +157,32 @@ Workspace::~Workspace() {
 
 
 // ---------------------------------------------------------------- Conv
+// convolution_param into the geometry members that Convolution and
+// Deconvolution both have
+template <class L>
+static void read_conv_param(L& l, const PMsgPtr& cp) {
+  l.Cout_ = (int)cp->inum("num_output");
+  CHECK_GT_(l.Cout_, 0) << "convolution_param.num_output must be positive";
+  const int k = (int)cp->inum("kernel_size", 0);
+  l.kh_ = k ? k : (int)cp->inum("kernel_h");
+  l.kw_ = k ? k : (int)cp->inum("kernel_w");
+  CHECK_GT_(l.kh_, 0);
+  const int s = (int)cp->inum("stride", 1);
+  l.sh_ = cp->has("stride_h") ? (int)cp->inum("stride_h") : s;
+  l.sw_ = cp->has("stride_w") ? (int)cp->inum("stride_w") : s;
+  const int p = (int)cp->inum("pad", 0);
+  l.ph_ = cp->has("pad_h") ? (int)cp->inum("pad_h") : p;
+  l.pw_ = cp->has("pad_w") ? (int)cp->inum("pad_w") : p;
+  l.dh_ = l.dw_ = (int)cp->inum("dilation", 1);
+  l.group_ = (int)cp->inum("group", 1);
+  l.bias_ = cp->boolean("bias_term", true);
+}
+
 void ConvolutionLayer::LayerSetUp(const std::vector<Blob*>& bottom,
                                   const std::vector<Blob*>&) {
   auto cp = param_->sub("convolution_param");
   CHECK_(cp) << "Convolution layer needs convolution_param";
-  Cout_ = (int)cp->inum("num_output");
-  CHECK_GT_(Cout_, 0) << "convolution_param.num_output must be positive";
-  const int k = (int)cp->inum("kernel_size", 0);
-  kh_ = k ? k : (int)cp->inum("kernel_h");
-  kw_ = k ? k : (int)cp->inum("kernel_w");
-  CHECK_GT_(kh_, 0);
-  const int s = (int)cp->inum("stride", 1);
-  sh_ = cp->has("stride_h") ? (int)cp->inum("stride_h") : s;
-  sw_ = cp->has("stride_w") ? (int)cp->inum("stride_w") : s;
-  const int p = (int)cp->inum("pad", 0);
-  ph_ = cp->has("pad_h") ? (int)cp->inum("pad_h") : p;
-  pw_ = cp->has("pad_w") ? (int)cp->inum("pad_w") : p;
-  dh_ = dw_ = (int)cp->inum("dilation", 1);
-  group_ = (int)cp->inum("group", 1);
-  bias_ = cp->boolean("bias_term", true);
+  read_conv_param(*this, cp);
   C_ = bottom[0]->channels();
   CHECK_EQ_(C_ % group_, 0);
   CHECK_EQ_(Cout_ % group_, 0);
@@ -273,6 +293,110 @@ void ConvolutionLayer::Backward_cpu(const std::vector<Blob*>& top,
     if (dx && !is1x1)
       cpu::col2im(dcol, C_, H_, W_, kh_, kw_, ph_, pw_, sh_, sw_, dh_, dw_,
                   dx + (long)n * C_ * H_ * W_);
+  }
+}
+
+// -------------------------------------------------------- Deconvolution
+void DeconvolutionLayer::LayerSetUp(const std::vector<Blob*>& bottom,
+                                    const std::vector<Blob*>&) {
+  auto cp = param_->sub("convolution_param");
+  CHECK_(cp) << "Deconvolution layer '" << name()
+             << "' needs convolution_param";
+  read_conv_param(*this, cp);
+  C_ = bottom[0]->channels();
+  CHECK_(C_ % group_ == 0)
+      << "Deconvolution layer '" << name() << "': " << C_
+      << " input channels are not a multiple of group " << group_;
+  CHECK_(Cout_ % group_ == 0)
+      << "Deconvolution layer '" << name() << "': num_output " << Cout_
+      << " is not a multiple of group " << group_;
+  if (blobs_.empty()) {
+    blobs_.emplace_back(new Blob({C_, Cout_ / group_, kh_, kw_}));
+    if (bias_) blobs_.emplace_back(new Blob({Cout_}));
+    Engine& E = Engine::get();
+    fill_blob(*blobs_[0], cp->sub("weight_filler"), E.cpu_rng);
+    if (bias_) fill_blob(*blobs_[1], cp->sub("bias_filler"), E.cpu_rng);
+  }
+}
+
+void DeconvolutionLayer::Reshape(const std::vector<Blob*>& bottom,
+                                 const std::vector<Blob*>& top) {
+  N_ = bottom[0]->num();
+  C_ = bottom[0]->channels();
+  H_ = bottom[0]->height();
+  W_ = bottom[0]->width();
+  OH_ = sh_ * (H_ - 1) + dh_ * (kh_ - 1) + 1 - 2 * ph_;
+  OW_ = sw_ * (W_ - 1) + dw_ * (kw_ - 1) + 1 - 2 * pw_;
+  CHECK_(OH_ > 0 && OW_ > 0)
+      << "Deconvolution layer '" << name() << "': top size " << OH_ << " x "
+      << OW_ << " is not positive";
+  S_ = (long)H_ * W_;
+  Spad_ = (S_ + 15) / 16 * 16;
+  top[0]->Reshape({N_, Cout_, OH_, OW_});
+  plan_gpu();
+}
+
+// The plain form, per image and group: y = col2im(Wᵀ·x) + b; with col =
+// im2col(dy): dW += x·colᵀ and dx = W·col.
+void DeconvolutionLayer::Forward_cpu(const std::vector<Blob*>& bottom,
+                                     const std::vector<Blob*>& top) {
+  const long cig = C_ / group_, K = (long)(Cout_ / group_) * kh_ * kw_;
+  const long OS = (long)OH_ * OW_;
+  float* dcol = (float*)Workspace::get_global().get(
+      Workspace::kDcol, sizeof(float) * (size_t)group_ * K * S_);
+  const float* x = bottom[0]->cpu_data();
+  const float* w = blobs_[0]->cpu_data();
+  float* y = top[0]->mutable_cpu_data();
+  for (int n = 0; n < N_; ++n) {
+    for (int g = 0; g < group_; ++g)
+      cpu::gemm(true, false, K, S_, cig, 1.f, w + g * cig * K,
+                x + ((long)n * C_ + g * cig) * S_, 0.f, dcol + g * K * S_);
+    float* yn = y + (long)n * Cout_ * OS;
+    cpu::col2im(dcol, Cout_, OH_, OW_, kh_, kw_, ph_, pw_, sh_, sw_, dh_,
+                dw_, yn);
+    if (bias_) {
+      const float* b = blobs_[1]->cpu_data();
+      for (int co = 0; co < Cout_; ++co)
+        for (long s = 0; s < OS; ++s) yn[co * OS + s] += b[co];
+    }
+  }
+}
+
+void DeconvolutionLayer::Backward_cpu(const std::vector<Blob*>& top,
+                                      const std::vector<bool>& prop_down,
+                                      const std::vector<Blob*>& bottom) {
+  const long cig = C_ / group_, K = (long)(Cout_ / group_) * kh_ * kw_;
+  const long OS = (long)OH_ * OW_;
+  float* col = (float*)Workspace::get_global().get(
+      Workspace::kCpuCol, sizeof(float) * (size_t)group_ * K * S_);
+  const float* x = bottom[0]->cpu_data();
+  const float* w = blobs_[0]->cpu_data();
+  const float* dy = top[0]->cpu_diff();
+  float* dw = blobs_[0]->mutable_cpu_diff();
+  float* dx = prop_down[0] ? bottom[0]->mutable_cpu_diff() : nullptr;
+  memset(dw, 0, sizeof(float) * blobs_[0]->count());
+  if (bias_) {
+    float* db = blobs_[1]->mutable_cpu_diff();
+    memset(db, 0, sizeof(float) * Cout_);
+    for (int n = 0; n < N_; ++n)
+      for (int co = 0; co < Cout_; ++co) {
+        const float* d = dy + ((long)n * Cout_ + co) * OS;
+        float acc = 0;
+        for (long s = 0; s < OS; ++s) acc += d[s];
+        db[co] += acc;
+      }
+  }
+  for (int n = 0; n < N_; ++n) {
+    cpu::im2col(dy + (long)n * Cout_ * OS, Cout_, OH_, OW_, kh_, kw_, ph_,
+                pw_, sh_, sw_, dh_, dw_, col);
+    for (int g = 0; g < group_; ++g) {
+      const long xo = ((long)n * C_ + g * cig) * S_;
+      cpu::gemm(false, true, cig, K, S_, 1.f, x + xo, col + g * K * S_, 1.f,
+                dw + g * cig * K);
+      if (dx)
+        cpu::gemm(false, false, cig, S_, K, 1.f, w + g * cig * K,
+                  col + g * K * S_, 0.f, dx + xo);
+    }
   }
 }
 
@@ -1450,6 +1574,7 @@ REGISTER_LAYER("Input", InputLayer)
 REGISTER_LAYER("Data", DataLayer)
 REGISTER_LAYER("DummyData", DataLayer)
 REGISTER_LAYER("Convolution", ConvolutionLayer)
+REGISTER_LAYER("Deconvolution", DeconvolutionLayer)
 REGISTER_LAYER("InnerProduct", InnerProductLayer)
 REGISTER_LAYER("Pooling", PoolingLayer)
 REGISTER_LAYER("Sigmoid", SigmoidLayer)

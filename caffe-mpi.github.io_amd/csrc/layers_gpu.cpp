@@ -126,6 +126,48 @@ static ConvGroup conv_group(const ConvolutionLayer& l, long ns) {
   return {cog * K, cig * l.H_ * l.W_, cog * l.S_, cog, K * ns};
 }
 
+// The operands of one conv's per-group GEMMs: Cout output channels of S
+// pixels (Spad padded) from K = C/group * kh * kw col rows per group.
+// Convolution passes its own geometry; Deconvolution's backward passes the
+// conv that maps its top gradient to its bottom.
+struct ConvGemms {
+  int group;
+  long Cout, K, S, Spad, NS;
+  ConvGroup o;
+};
+static ConvGemms conv_gemms(const ConvolutionLayer& l) {
+  const long NS = (long)l.N_ * l.Spad_;
+  return {l.group_, l.Cout_, (long)l.C_ / l.group_ * l.kh_ * l.kw_,
+          l.S_,     l.Spad_, NS,
+          conv_group(l, NS)};
+}
+// y = W·B per group, scattered to NCHW by epi (bias per group added there):
+// B is x through the view xv, or, with col, the col buffer b
+static void conv_fwd_gemms(const ConvGemms& c, const float* w, const float* b,
+                           bool col, const GemmView& xv, GemmEpi epi,
+                           const float* bias, float* y) {
+  hipStream_t s = Engine::get().stream;
+  for (int g = 0; g < c.group; ++g) {
+    epi.bias = bias ? bias + g * c.o.bias : nullptr;
+    gpu::gemm(s, false, false, c.Cout / c.group, c.NS, c.K, 1.f,
+              w + g * c.o.w, c.K, b + g * (col ? c.o.col : c.o.x),
+              col ? c.NS : 0, 0.f, y + g * c.o.y, c.S, &epi, nullptr,
+              col ? nullptr : &xv);
+  }
+}
+// dW = dY-view · Bᵀ per group, B as in forward
+static void conv_wgrad_gemms(const ConvGemms& c, const float* dy,
+                             const float* b, bool col, const GemmView& xv,
+                             float* dw) {
+  hipStream_t s = Engine::get().stream;
+  const GemmView dyv{c.Spad, c.S, c.Cout};  // dY[N][Cout][S] as [Cout][N*Spad]
+  for (int g = 0; g < c.group; ++g)
+    gpu::gemm(s, false, true, c.Cout / c.group, c.K, c.NS, 1.f,
+              dy + g * c.o.y, 0, b + g * (col ? c.o.col : c.o.x),
+              col ? c.NS : 0, 0.f, dw + g * c.o.w, c.K, nullptr, &dyv,
+              col ? nullptr : &xv);
+}
+
 // NCHW-scatter epilogue: column n*spad + s of GEMM row r lands at
 // C[(n*chan + r)*S + s]
 static GemmEpi nchw_scatter(long spad, long S, long chan) {
@@ -147,7 +189,6 @@ static GemmView conv_x_view(const ConvolutionLayer& l) {
 void ConvolutionLayer::Forward_gpu(const std::vector<Blob*>& bottom,
                                    const std::vector<Blob*>& top) {
   Engine& E = Engine::get();
-  const int K = C_ / group_ * kh_ * kw_;
   const long NS = (long)N_ * Spad_;
   const float* x = bottom[0]->gpu_data();
   const float* w = blobs_[0]->gpu_data();
@@ -173,13 +214,7 @@ void ConvolutionLayer::Forward_gpu(const std::vector<Blob*>& bottom,
   }
   GemmEpi epi = nchw_scatter(Spad_, S_, Cout_);
   epi.relu = fuse_relu_;
-  const ConvGroup o = conv_group(*this, NS);
-  for (int g = 0; g < group_; ++g) {
-    epi.bias = bias ? bias + g * o.bias : nullptr;
-    gpu::gemm(E.stream, false, false, Cout_ / group_, NS, K, 1.f,
-              w + g * o.w, K, b + g * (col ? o.col : o.x), col ? NS : 0, 0.f,
-              y + g * o.y, S_, &epi, nullptr, col ? nullptr : &xv);
-  }
+  conv_fwd_gemms(conv_gemms(*this), w, b, col, xv, epi, bias, y);
 }
 
 void ConvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
@@ -224,10 +259,7 @@ void ConvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
   const float* b = col ? (const float*)col_.p : x;
   float* dw = blobs_[0]->mutable_gpu_diff();
   const ConvGroup o = conv_group(*this, NS);
-  for (int g = 0; g < group_; ++g)
-    gpu::gemm(E.stream, false, true, Cout_ / group_, K, NS, 1.f,
-              dy + g * o.y, 0, b + g * (col ? o.col : o.x), col ? NS : 0,
-              0.f, dw + g * o.w, K, nullptr, &dyv, col ? nullptr : &xv);
+  conv_wgrad_gemms(conv_gemms(*this), dy, b, col, xv, dw);
   if (!prop_down[0]) return;
 
   float* dx = bottom[0]->mutable_gpu_diff();
@@ -293,6 +325,92 @@ void ConvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
     case kGcGather:
       break;
   }
+}
+
+// -------------------------------------------------------- Deconvolution
+// Forward is the backward-data of the conv that maps the top to the bottom
+// (layers.hpp).  At stride > 1 and dilation 1 it takes the phase-split
+// kernels of kernels/deconv.hip: no dcol matrix, bias in the epilogue
+// (deconv_supported: the window fits LDS, 32-bit indices).  Inside that
+// route deconv.hip picks its direct variant at Cout/group <= 4 and the MFMA
+// variant above; that threshold is a policy constant and has NOT been
+// measured.  Stride 1, dilation > 1 and CAFFE_DECONV=0 take the form the
+// conv dgrad's kCol2im has: dcol = Wᵀ·x per group, col2im_batched, then a
+// bias pass.  Backward is the explicit-col conv of the top gradient: one
+// im2col into col_ serves the wgrad GEMMs and, when it propagates, the
+// forward GEMMs that give dx; both are Convolution's own GEMM loops.
+static float* zeros_ones(Blob& zo, int C);
+
+static gpu::Deconv dc_geom(const DeconvolutionLayer& l) {
+  return {l.N_, l.group_, l.C_ / l.group_, l.Cout_ / l.group_,
+          l.H_, l.W_,     l.OH_,           l.OW_,
+          l.kh_, l.kw_,   l.sh_,           l.sw_,
+          l.ph_, l.pw_};
+}
+void DeconvolutionLayer::plan_gpu() {
+  static const bool split_ok = [] {
+    const char* e = getenv("CAFFE_DECONV");
+    return e ? atoi(e) != 0 : true;
+  }();
+  phase_split_ = split_ok && dh_ == 1 && dw_ == 1 && (sh_ > 1 || sw_ > 1) &&
+                 gpu::deconv_supported(dc_geom(*this));
+}
+
+// the conv from the top [N][Cout][OH][OW] to the bottom [N][C][H][W]: its
+// output channels are C_, its col rows Cout/group * kh * kw per group
+static ConvGemms deconv_gemms(const DeconvolutionLayer& l) {
+  const long NS = (long)l.N_ * l.Spad_;
+  const long cig = l.C_ / l.group_, cog = l.Cout_ / l.group_;
+  const long K = cog * l.kh_ * l.kw_;
+  return {l.group_, l.C_, K, l.S_, l.Spad_, NS,
+          {cig * K, cog * l.OH_ * l.OW_, cig * l.S_, cig, K * NS}};
+}
+
+void DeconvolutionLayer::Forward_gpu(const std::vector<Blob*>& bottom,
+                                     const std::vector<Blob*>& top) {
+  Engine& E = Engine::get();
+  const float* x = bottom[0]->gpu_data();
+  const float* w = blobs_[0]->gpu_data();
+  const float* bias = bias_ ? blobs_[1]->gpu_data() : nullptr;
+  float* y = top[0]->mutable_gpu_data();
+  if (phase_split_) {
+    gpu::deconv_fwd(E.stream, dc_geom(*this), x, w, bias, y);
+    return;
+  }
+  const ConvGemms c = deconv_gemms(*this);
+  float* dcol = (float*)Workspace::get_global().get(
+      Workspace::kDcol, sizeof(float) * (size_t)group_ * c.o.col);
+  const GemmView xv{Spad_, S_, C_};  // x[N][C][S] as [C][N*Spad]
+  for (int g = 0; g < group_; ++g)
+    gpu::gemm(E.stream, true, false, c.K, c.NS, C_ / group_, 1.f,
+              w + g * c.o.w, c.K, x + g * c.o.y, 0, 0.f, dcol + g * c.o.col,
+              c.NS, nullptr, nullptr, &xv);
+  gpu::col2im_batched(E.stream, dcol, N_, Cout_, OH_, OW_, kh_, kw_, ph_, pw_,
+                      sh_, sw_, dh_, dw_, H_, W_, Spad_, y);
+  if (bias)  // y = y*1 + b[c]
+    gpu::chan_affine(E.stream, y, zeros_ones(zo_, Cout_) + Cout_, bias, N_,
+                     Cout_, (long)OH_ * OW_, y);
+}
+
+void DeconvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
+                                      const std::vector<bool>& prop_down,
+                                      const std::vector<Blob*>& bottom) {
+  Engine& E = Engine::get();
+  const float* dy = top[0]->gpu_diff();
+  if (bias_)
+    gpu::bias_grad(E.stream, dy, N_, Cout_, (long)OH_ * OW_,
+                   blobs_[1]->mutable_gpu_diff());
+  const ConvGemms c = deconv_gemms(*this);
+  float* col = (float*)col_.reserve(sizeof(float) * (size_t)group_ * c.o.col);
+  gpu::im2col_batched(E.stream, dy, N_, Cout_, OH_, OW_, kh_, kw_, ph_, pw_,
+                      sh_, sw_, dh_, dw_, H_, W_, Spad_, col);
+  // the wgrad's "dY" is the bottom data: dW[ci][co, ki, kj] = x · colᵀ
+  conv_wgrad_gemms(c, bottom[0]->gpu_data(), col, true, GemmView{},
+                   blobs_[0]->mutable_gpu_diff());
+  if (prop_down[0])
+    conv_fwd_gemms(c, blobs_[0]->gpu_data(), col, true, GemmView{},
+                   nchw_scatter(Spad_, S_, C_), nullptr,
+                   bottom[0]->mutable_gpu_diff());
 }
 
 // -------------------------------------------------------------------- IP

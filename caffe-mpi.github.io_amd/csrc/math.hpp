@@ -310,6 +310,9 @@ void gemm_trace_readers(long* cursor, long* wide64);
 //       tiles per image> pairs=<output channels per thread (3x3)>
 //       slices=<batch slices> bias=<0|1> splits=<threads sharing an owner's
 //       pixels> blocks=<first-stage grid>
+//   op=deconv_fwd var=mfma|direct phases=<sh*sw> chunks=<input-channel
+//       chunks per block> tiles_y=<cell tiles per plane> tiles_x=<likewise>
+//       blocks=<grid>
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
 // The depthwise wrappers (kernels/depthwise.hip) record into the same log:
@@ -360,6 +363,28 @@ void gconv_bwd_data(hipStream_t s, const GConv& g, const float* dy,
 // dw (and db = Σ dy when db is given) overwritten; two-stage, deterministic
 void gconv_bwd_weight(hipStream_t s, const GConv& g, const float* x,
                       const float* dy, float* dw, float* db);
+
+// The deconvolution wrapper (kernels/deconv.hip) likewise: var 0 mfma,
+// 1 direct.
+void kernel_trace_deconv(int var, long phases, long chunks, long tiles_y,
+                         long tiles_x, long blocks);
+
+// Forward of a transposed convolution at stride > 1 and dilation 1:
+// x[N][G*cig][H][W], w[G*cig][cog][kh][kw] (the Deconvolution layer's blob),
+// y[N][G*cog][OH][OW] with OH = sh*(H-1) + kh - 2*ph; group g maps input
+// channels g*cig.. to output channels g*cog...  Split by stride phase, no
+// dcol matrix (deconv.hip).
+struct Deconv {
+  int N, G, cig, cog, H, W, OH, OW, kh, kw, sh, sw, ph, pw;
+};
+// false when the smallest window does not fit the LDS budget or a tensor
+// (the packed weights included) has 2^31 elements or more; the layer then
+// keeps the GEMM + col2im route
+bool deconv_supported(const Deconv& g);
+// y = deconv(x, w) (+ bias), every element written once; packs the weights
+// into the kDeconvW workspace slot first
+void deconv_fwd(hipStream_t s, const Deconv& g, const float* x,
+                const float* w, const float* bias, float* y);
 
 // db[c] = Σ_n Σ_s dy[n][c][s] (deterministic)
 void bias_grad(hipStream_t s, const float* dy, int N, int C, long S,

@@ -243,7 +243,11 @@ int caffe_gemm_trace_readers(long* cursor, long* wide64);
  * var=k3s1 cig=4 cog=4 chunks=1 pairs=1 slices=1 bias=1 splits=16 blocks=8"
  * (var k3s1 | k3s2 | generic; staged tiles per image, output channels per
  * thread, batch slices, bias summed, threads sharing an owner's pixels,
- * first-stage grid). */
+ * first-stage grid).  A Deconvolution layer (reached like every layer:
+ * prototxt, net, no entry point of its own) at stride > 1 and dilation 1
+ * records "op=deconv_fwd var=mfma phases=4 chunks=1 tiles_y=1 tiles_x=1
+ * blocks=2" per forward (var mfma | direct; stride phases sh*sw; input-
+ * channel chunks per block; cell tiles per plane; launch grid). */
 int caffe_kernel_trace(int enable);
 int caffe_kernel_trace_read(char* buf, int cap);
 /* The graph fusions planned for a net at build time, same buffer contract
