@@ -18,6 +18,10 @@ from engine_util import TOL, input_net, net_from_text, relerr, run_layer
 
 GPU = pytest.param("gpu", marks=pytest.mark.gpu)
 
+# Kernel of deconv.hip each row launches (extend the rows of the one you edit):
+# mfma<1,2> V1 | mfma<2,2> V2 | mfma<1,4> T2 T4-T9 V3 V4 V6 V7 V8 V13
+# | mfma<2,4> T1 T3 V5 V14 | direct<1> T10 V12 | direct<2> V9
+# | direct<4> V10 V11 | none (GEMM + col2im) S1 D2 R1
 # id: (N, Ci, Co, group, H, W, kernel, stride, pad, bias, dilation, var)
 ROWS = {
     "T1": (2, 32, 64, 1, 5, 5, 4, 2, 1, True, 1, "mfma"),
@@ -33,6 +37,46 @@ ROWS = {
     # the fallback boundary: stride 1, dilation 2
     "S1": (2, 16, 24, 1, 6, 7, 3, 1, 1, True, 1, None),
     "D2": (2, 16, 24, 2, 5, 6, 3, 2, 1, True, 2, None),
+    # P == 2: stride along one axis only; pad >= stride on the stride-1 axis
+    "V1": (2, 16, 24, 1, 5, 6, (4, 3), (2, 1), (1, 1), True, 1, "mfma"),
+    # the paired 8-byte store with an odd OW (13)
+    "V2": (2, 16, 40, 1, 5, 6, (3, 3), (1, 2), (1, 0), False, 1, "mfma"),
+    # pad >= stride (dq > 0): the k5 s2 p2 layer; OH = 9 is odd
+    "V3": (2, 32, 32, 1, 5, 6, 5, 2, 2, True, 1, "mfma"),
+    # dq = (2, 1), phases whose dq differs along H, two passes of phases
+    "V4": (2, 16, 16, 1, 6, 5, (7, 6), (2, 3), (5, 3), False, 1, "mfma"),
+    # Cout/group 96: two channel tiles of 64, the second half empty
+    "V5": (2, 20, 192, 2, 4, 5, 4, 2, 1, True, 1, "mfma"),
+    # odd C/group: the zeroed second channel of the last k-pair
+    "V6": (2, 7, 8, 1, 5, 5, 3, 2, 1, True, 1, "mfma"),
+    # a last chunk of one channel; chunks >= 2 with more than four phases
+    "V7": (1, 33, 16, 1, 4, 4, 3, 3, 1, False, 1, "mfma"),
+    # the FCN 21-class 8x upsampler, ungrouped: 64 phases in 16 passes
+    "V8": (1, 21, 21, 1, 3, 3, 16, 8, 4, False, 1, "mfma"),
+    # direct, two channels per thread, 2 x 2 cell tiles
+    "V9": (1, 12, 8, 4, 10, 20, 4, 2, 1, True, 1, "direct"),
+    # direct, Cout/group 3 padded to 4: the pad channel is not stored
+    "V10": (2, 8, 6, 2, 5, 6, 3, 2, 0, True, 1, "direct"),
+    "V11": (2, 5, 20, 5, 4, 5, (5, 4), (3, 2), (2, 1), False, 1, "direct"),
+    "V12": (2, 3, 3, 3, 5, 6, 5, 2, 2, True, 1, "direct"),
+    # the window, not the channel count, sets the chunk: 16 of 32 channels
+    "V13": (1, 32, 32, 1, 2, 2, 24, 2, 0, False, 1, "mfma"),
+    # three chunks and three passes of phases
+    "V14": (2, 96, 40, 1, 3, 3, 3, 3, 0, True, 1, "mfma"),
+    # Cout/group <= 4 with C/group > 4: refused, keeps the GEMM route
+    "R1": (2, 16, 3, 1, 5, 5, 4, 2, 1, True, 1, None),
+}
+
+# what dc_plan() of deconv.hip gives for a row, as the deconv_fwd record shows
+PLAN = {
+    "V1": {"chunks": 1},
+    "V2": {"blocks": 2},
+    "V5": {"blocks": 8},
+    "V6": {"chunks": 1},
+    "V7": {"chunks": 2},
+    "V9": {"tiles_y": 2, "tiles_x": 2, "blocks": 16},
+    "V13": {"chunks": 2, "tiles_y": 2},
+    "V14": {"chunks": 3},
 }
 
 
@@ -40,11 +84,11 @@ def pair(v):
     return v if isinstance(v, tuple) else (v, v)
 
 
-def layer_text(row, relu=False, extra=""):
+def layer_text(row, relu=False, extra="", name="up", bottom="in0", top="out"):
     Co, g, bias, d = row[2], row[3], row[9], row[10]
     (kh, kw), (sh, sw), (ph, pw) = pair(row[6]), pair(row[7]), pair(row[8])
     text = f"""layer {{
-  name: "up" type: "Deconvolution" bottom: "in0" top: "out"
+  name: "{name}" type: "Deconvolution" bottom: "{bottom}" top: "{top}"
   convolution_param {{
     num_output: {Co} group: {g} dilation: {d}
     kernel_h: {kh} kernel_w: {kw} stride_h: {sh} stride_w: {sw}
@@ -109,7 +153,7 @@ def check_values(got, ref):
 
 
 @pytest.mark.parametrize("mode", ["cpu", GPU])
-@pytest.mark.parametrize("rid", [r for r in ROWS if r.startswith("T")])
+@pytest.mark.parametrize("rid", [r for r in ROWS if r[0] in "TV"])
 def test_matches_conv_transpose2d(rid, mode):
     row = ROWS[rid]
     _, got, recs, gemms = run_row(mode, rid)
@@ -118,6 +162,8 @@ def test_matches_conv_transpose2d(rid, mode):
         assert gemms == []
         assert len(recs) == 1 and recs[0]["phases"] == sh * sw, recs
         assert row[11] is None or recs[0]["var"] == row[11], recs
+        want = PLAN.get(rid, {})
+        assert {k: recs[0][k] for k in want} == want, recs
         if rid == "T7":
             assert recs[0]["tiles_y"] >= 2 and recs[0]["tiles_x"] >= 2
         if rid == "T8":
@@ -131,6 +177,141 @@ def test_stride1_and_dilation_stay_on_gemm(rid):
     _, got, recs, gemms = run_row("gpu", rid)
     assert recs == [] and len(gemms) >= ROWS[rid][3], (recs, gemms)
     check_values(got, case(rid)[4])
+
+
+@pytest.mark.parametrize("mode", ["cpu", GPU])
+def test_refused_zone_stays_on_gemm(mode):
+    """Cout/group <= 4 with C/group > 4 is refused by deconv_supported()"""
+    _, got, recs, gemms = run_row(mode, "R1")
+    if mode == "gpu":
+        assert recs == [] and len(gemms) >= ROWS["R1"][3], (recs, gemms)
+    check_values(got, case("R1")[4])
+
+
+def traced_forward(net):
+    """net.forward() with the kernel trace on: its deconv_fwd records"""
+    ca.kernel_trace(True)
+    try:
+        net.forward()
+    finally:
+        ca.kernel_trace(False)
+    return [k for k in ca.kernel_trace_read() if k["op"] == "deconv_fwd"]
+
+
+def row_net(mode, rid):
+    """run_row() up to the forward: the net with its input and params set"""
+    x, w, b, _, _ = case(rid)
+    ca.set_mode(mode)
+    net = net_from_text(input_net([x.shape], layer_text(ROWS[rid])))
+    net.set_blob("in0", x)
+    for i, p in enumerate([w] if b is None else [w, b]):
+        net.set_param(i, p.ravel())
+    return net
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rid", ["T1", "T2", "V2", "V5", "V9", "V10"])
+def test_every_output_element_is_written(rid):
+    """The top starts as NaN, not as the zeros a fresh blob holds: an element
+    the kernel skips cannot pass as a small value"""
+    ref = case(rid)[4]
+    net = row_net("gpu", rid)
+    net.set_blob("out", np.full(ref[0].shape, np.nan, np.float32))
+    assert np.isnan(net.blob("out")).all()
+    assert len(traced_forward(net)) == 1
+    y = net.blob("out")
+    assert np.isfinite(y).all(), np.argwhere(~np.isfinite(y))[:8]
+    check_values([y], ref[:1])
+
+
+@pytest.mark.parametrize("mode", ["cpu", GPU])
+def test_new_weights_are_packed_again(mode):
+    """The packed copy of the weights is made per forward: after set_param
+    the next forward computes with the new ones"""
+    rid = "V3"
+    x, w, b, _, ref = case(rid)
+    net = row_net(mode, rid)
+    net.forward()
+    y1 = net.blob("out")
+    check_values([y1], ref[:1])
+    r = np.random.default_rng(5)
+    w2 = (r.standard_normal(w.shape) * 0.3).astype(np.float32)
+    b2 = r.standard_normal(b.shape).astype(np.float32)
+    net.set_param(0, w2.ravel())
+    net.set_param(1, b2)
+    recs = traced_forward(net)
+    assert mode == "cpu" or len(recs) == 1, recs
+    y2 = net.blob("out")
+    s, p = pair(ROWS[rid][7]), pair(ROWS[rid][8])
+    ref2 = torch.nn.functional.conv_transpose2d(
+        *(torch.tensor(a, dtype=torch.float64) for a in (x, w2, b2)),
+        stride=s, padding=p).numpy()
+    check_values([y2], [ref2])
+    assert relerr(y2, y1) > 0.1
+
+
+# up2 on the 8 channels of up1 (row V6): Cout 96, so its packed weights are
+# larger than up1's and the workspace slot they share grows between the two
+UP2 = (2, 8, 96, 1, 9, 9, 4, 2, 1, True, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def two_layer_case():
+    """(x, [w1, b1, w2, b2], dy, [y, dx, dW1, db1, dW2, db2]) of in0 -> up1
+    (row V6) -> up2 (UP2), float64"""
+    r = np.random.default_rng(77)
+    x = case("V6")[0]
+    params = []
+    for row in (ROWS["V6"], UP2):
+        shape = (row[1], row[2] // row[3]) + pair(row[6])
+        params += [(r.standard_normal(shape) * 0.3).astype(np.float32),
+                   r.standard_normal(row[2]).astype(np.float32)]
+    tx, *tp = (torch.tensor(a, dtype=torch.float64, requires_grad=True)
+               for a in [x] + params)
+    y = tx
+    for i, row in enumerate((ROWS["V6"], UP2)):
+        y = torch.nn.functional.conv_transpose2d(
+            y, tp[2 * i], tp[2 * i + 1], stride=pair(row[7]),
+            padding=pair(row[8]))
+    dy = r.standard_normal(tuple(y.shape)).astype(np.float32)
+    y.backward(torch.tensor(dy, dtype=torch.float64))
+    return x, params, dy, [y.detach().numpy(), tx.grad.numpy()] + \
+        [p.grad.numpy() for p in tp]
+
+
+@pytest.mark.parametrize("mode", ["cpu", GPU])
+def test_two_layers_share_the_weight_slot(mode):
+    """A decoder's shape: two Deconvolution layers of different size in one
+    net, forward and backward twice without rebuilding"""
+    x, params, dy, ref = two_layer_case()
+    ca.set_mode(mode)
+    net = net_from_text(input_net(
+        [x.shape], layer_text(ROWS["V6"], name="up1", top="mid") + "\n" +
+        layer_text(UP2, name="up2", bottom="mid")))
+    net.set_blob("in0", x)
+    # the net lists its params in an order of its own: find them by layer
+    at = {info[:2]: i for i, info in net.params().items()}
+    idx = [at[key] for key in (("up1", 0), ("up1", 1), ("up2", 0), ("up2", 1))]
+    for i, p in zip(idx, params):
+        net.set_param(i, p.ravel())
+    runs = []
+    for _ in range(2):
+        recs = traced_forward(net)
+        if mode == "gpu":
+            assert [k["var"] for k in recs] == ["mfma", "mfma"], recs
+        y = net.blob("out")
+        net.set_blob("out", dy, diff=True)
+        net.backward()
+        got = [y, net.blob("in0", diff=True)] + \
+            [net.param(i, diff=True) for i in idx]
+        for name, a, b in zip(("y", "dx", "dW1", "db1", "dW2", "db2"), got,
+                              ref):
+            err = relerr(a, b)
+            print(name, err)
+            assert err < TOL, (name, err)
+        runs.append(got)
+    for a, b in zip(*runs):
+        assert np.array_equal(a, b)
 
 
 # torch-free (its bundled ROCm runtime must not load after the engine's)
@@ -172,8 +353,10 @@ def test_env_switch_forces_the_fallback(tmp_path):
 
 
 @pytest.mark.gpu
-def test_rerun_is_bit_identical():
-    runs = [[np.asarray(a).copy() for a in run_row("gpu", "T1")[1][:3]]
+@pytest.mark.parametrize("rid", ["T1", "V2", "V9", "V14"])
+def test_rerun_is_bit_identical(rid):
+    """mfma<2,4>, the paired store, direct, and several chunks and passes"""
+    runs = [[np.asarray(a).copy() for a in run_row("gpu", rid)[1][:3]]
             for _ in range(2)]
     for a, b in zip(*runs):
         assert np.array_equal(a, b)
