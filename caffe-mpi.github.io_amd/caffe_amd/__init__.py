@@ -286,7 +286,10 @@ def kernel_trace_read():
     (output channels per thread), slices, bias, splits, blocks.  A
     Deconvolution forward at stride > 1 and dilation 1 records deconv_fwd
     with var (mfma | direct), phases (sh * sw), chunks (input-channel chunks
-    per block), tiles_y, tiles_x, blocks."""
+    per block), tiles_y, tiles_x, blocks; its backward with at most 4
+    channels per group on both sides records deconv_bwd_weight with var,
+    phases, chunks (windows staged per block), slices, blocks and
+    deconv_bwd_data with var, phases, chunks, tiles_y, tiles_x, blocks."""
     return _trace_records(_lib.caffe_kernel_trace_read)
 
 

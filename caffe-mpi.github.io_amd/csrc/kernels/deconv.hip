@@ -1,5 +1,6 @@
 // deconv.hip — forward of the Deconvolution layer (transposed convolution)
-// at stride > 1, dilation 1, for gfx950: the output is split by stride phase
+// at stride > 1, dilation 1, for gfx950, and backward for few channels per
+// group (second half of the file): the output is split by stride phase
 // and each phase is a dense stride-1 correlation, so no dcol matrix is ever
 // written and no tap multiplies an inserted zero.
 //
@@ -168,6 +169,22 @@ __host__ __device__ inline DcPhase dc_phase(int r, int pad, int s, int k,
   return {rk, dq - dqmin + tmax - 1, rk < k ? (k - rk + s - 1) / s : 0};
 }
 
+// W[g * cig + ci][co][ki][kj] at tap `slot` of phase p; zero for a tap the
+// phase does not have and for pad channels
+__device__ inline float dc_pack_value(const Deconv& g, int tmh, int tmw,
+                                      int dqh, int dqw,
+                                      const float* __restrict__ w, int grp,
+                                      int p, int slot, int ci, int co) {
+  const int tt = slot / tmw, u = slot - tt * tmw;
+  const int r = p / g.sw, s = p - r * g.sw;
+  const DcPhase fh = dc_phase(r, g.ph, g.sh, g.kh, tmh, dqh);
+  const DcPhase fw = dc_phase(s, g.pw, g.sw, g.kw, tmw, dqw);
+  if (tt >= fh.T || u >= fw.T || ci >= g.cig || co >= g.cog) return 0.f;
+  return w[(((grp * g.cig + ci) * g.cog + co) * g.kh + fh.rk + g.sh * tt) *
+               g.kw +
+           fw.rk + g.sw * u];
+}
+
 // Wp[g][p][slot][ci][co] from W[g * cig + ci][co][kh][kw]; pads are zero
 __global__ void k_deconv_pack_w(Deconv g, DcPlan t,
                                 const float* __restrict__ w,
@@ -181,17 +198,8 @@ __global__ void k_deconv_pack_w(Deconv g, DcPlan t,
     e /= t.cigp;
     const int slot = e % t.slots;
     e /= t.slots;
-    const int p = e % t.P, grp = e / t.P;
-    const int tt = slot / t.tmw, u = slot - tt * t.tmw;
-    const int r = p / g.sw, s = p - r * g.sw;
-    const DcPhase fh = dc_phase(r, g.ph, g.sh, g.kh, t.tmh, t.dqh);
-    const DcPhase fw = dc_phase(s, g.pw, g.sw, g.kw, t.tmw, t.dqw);
-    float v = 0.f;
-    if (tt < fh.T && u < fw.T && ci < g.cig && co < g.cog)
-      v = w[(((grp * g.cig + ci) * g.cog + co) * g.kh + fh.rk + g.sh * tt) *
-                g.kw +
-            fw.rk + g.sw * u];
-    wp[i] = v;
+    wp[i] = dc_pack_value(g, t.tmh, t.tmw, t.dqh, t.dqw, w, e / t.P, e % t.P,
+                          slot, ci, co);
   }
 }
 
@@ -199,7 +207,8 @@ __global__ void k_deconv_pack_w(Deconv g, DcPlan t,
 struct DcBlock {
   int n, grp, ct, q0h, q0w;
 };
-__device__ inline DcBlock dc_block(const Deconv& g, const DcPlan& t) {
+template <class Plan>  // DcPlan, or backward's DbPlan (cells of the input)
+__device__ inline DcBlock dc_block(const Deconv& g, const Plan& t) {
   int b = blockIdx.x;
   const int txi = b % t.tx;
   b /= t.tx;
@@ -410,6 +419,344 @@ __global__ __launch_bounds__(kTPB) void k_deconv_direct(
   }
 }
 
+// =============================================================== backward
+// For forward's direct zone only (both channel counts per group <= 4:
+// bilinear upsampling with group == channels), where the im2col + GEMM route
+// is at its worst.  MFMA variants of both passes were written and measured
+// (profiles/deconv.txt, "backward"): they lost to im2col + GEMMs by 1.8x at
+// 256 -> 128 k4 s2 and 4.2x at 128 -> 64 k2 s2, so every layer outside the
+// direct zone is refused here and keeps that route.
+//
+// Cells are now the INPUT pixels (h, w).  Phase (r, s) of the top gradient,
+// dy_rs[q] = dy[sh*q + r][sw*q' + s], reaches input row h through tap t at
+// cell row q = h - dq(r) + t, so a tile of TQH x kTQW input cells needs the
+// cell rows from q0 - dqmin - ddh on, LH = TQH + tmh - 1 + ddh of them: the
+// forward window's extent, per phase.
+constexpr int kBwdBlocks = 1024;  // wgrad grid aimed at: 4 blocks per CU
+// Most split-K slices of wgrad.  The partials are slices x cell splits x the
+// padded dW, written once and read once by the reduce: at 32 slices of 16
+// splits a k4 layer of 512 one-channel groups holds 16 MB of them, and a
+// thread still accumulates 1 / 32 of its cells in registers.  A policy
+// constant, NOT measured.
+constexpr int kMaxSlices = 32;
+
+enum { kBwdData = 0, kBwdWeight = 1 };
+
+struct DbPlan {
+  int var;
+  int P, tmh, tmw, slots, dqh, dqw, ddh, ddw;  // forward's phase geometry
+  int TQH, ty, tx;         // input-cell rows per tile (columns: kTQW), tiles
+  int LH, LW, plane, per;  // window per phase; plane = LH * LW; P planes | 1
+  int cc, chunks;          // dy channels staged; chunks of them (1)
+  int mt, cot;             // CB: padded channels per group; channel tiles (1)
+  int cells, xst;          // TQH * kTQW; wgrad's x tile stride
+  int items, ipb, slices;  // wgrad: (image, tile) items; per slice; slices
+  int tpt, nsplit, passes; // wgrad: threads along the taps; threads sharing
+                           // a tap, each with its own cells; tap passes
+  int win_floats, wl_floats, x_floats;
+  long pstride;            // WpT floats per (group, phase): slots * cog * CB
+  long part_floats;        // wgrad partials
+  int blocks;
+  bool fits;
+  FastDiv fd_area, fd_rw, fd_sh, fd_sw, fd_cells;
+};
+
+DbPlan db_plan(const Deconv& g, int pass) {
+  const DcPlan f = dc_plan(g);
+  DbPlan t{};
+  // outside the direct zone: refused, see above
+  if (g.cog > kDirectMaxCog || g.cig > kDirectMaxCig) return t;
+  t.P = f.P, t.tmh = f.tmh, t.tmw = f.tmw, t.slots = f.slots;
+  t.dqh = f.dqh, t.dqw = f.dqw;
+  t.ddh = (g.sh - 1 + g.ph) / g.sh - t.dqh;
+  t.ddw = (g.sw - 1 + g.pw) / g.sw - t.dqw;
+  t.LW = kTQW + t.tmw - 1 + t.ddw;
+  t.tx = ceil_div(g.W, kTQW);
+  const int khkw = g.kh * g.kw;
+  auto per = [&](int tqh) {
+    return (t.P * (tqh + t.tmh - 1 + t.ddh) * t.LW) | 1;
+  };
+  // window of every output channel, dgrad's packed weights or wgrad's x
+  // tile beside it; CB pads both channel counts
+  const int m = std::max(g.cig, g.cog), CB = m == 1 ? 1 : m == 2 ? 2 : 4;
+  auto xfl = [&](int tqh) {
+    return pass == kBwdWeight ? CB * (tqh * kTQW + 1) : 0;
+  };
+  t.var = kVarDirect;
+  t.mt = CB;
+  t.cot = 1;
+  t.cc = pass == kBwdWeight ? CB : g.cog;
+  t.chunks = 1;
+  t.pstride = (long)t.slots * g.cog * CB;
+  t.wl_floats = pass == kBwdData ? (int)(t.P * t.pstride) : 0;
+  t.TQH = 16;
+  auto floats = [&](int tqh) {
+    return (long)round_up(t.cc * per(tqh), 4) + t.wl_floats + xfl(tqh);
+  };
+  while (floats(t.TQH) > kLdsFloats && t.TQH > 1) t.TQH /= 2;
+  t.fits = floats(t.TQH) <= kLdsFloats;
+  t.tpt = std::min(khkw, kTPB);
+  t.nsplit = kTPB / t.tpt;
+  t.passes = ceil_div(khkw, t.tpt);
+  t.LH = t.TQH + t.tmh - 1 + t.ddh;
+  t.plane = t.LH * t.LW;
+  t.per = per(t.TQH);
+  t.win_floats = round_up(t.cc * t.per, 4);
+  t.cells = t.TQH * kTQW;
+  t.xst = t.cells + 1;
+  t.x_floats = xfl(t.TQH);
+  t.ty = ceil_div(g.H, t.TQH);
+  if (pass == kBwdData) {
+    t.blocks = g.N * g.G * t.ty * t.tx;
+  } else {
+    t.items = g.N * t.ty * t.tx;
+    const int want = std::min(
+        {t.items, kMaxSlices, std::max(1, ceil_div(kBwdBlocks, g.G))});
+    t.ipb = ceil_div(t.items, want);
+    t.slices = ceil_div(t.items, t.ipb);
+    t.blocks = t.slices * g.G;
+    t.part_floats = (long)t.slices * t.nsplit * g.G * khkw * CB * CB;
+  }
+  t.fd_area = fastdiv_make((unsigned long)t.plane * g.sh * g.sw);
+  t.fd_rw = fastdiv_make((unsigned long)t.LW * g.sw);
+  t.fd_sh = fastdiv_make(g.sh);
+  t.fd_sw = fastdiv_make(g.sw);
+  t.fd_cells = fastdiv_make(t.cells);
+  return t;
+}
+
+bool db_counts_fit(const Deconv& g, const DbPlan& t) {
+  const long lim = 1L << 31;
+  return (long)g.N * g.G * g.cig * g.H * g.W < lim &&
+         (long)g.N * g.G * g.cog * g.OH * g.OW < lim &&
+         (long)g.G * t.P * t.pstride < lim / 2 && t.part_floats < lim &&
+         (long)g.N * g.G * t.ty * t.tx < lim;
+}
+
+// WpT[g][p][slot][co][ci]: ci innermost and padded to CB, the channels a
+// dgrad thread accumulates, so its weights of one (tap, co) are one LDS
+// vector; pads are zero
+__global__ void k_deconv_pack_wt(Deconv g, DbPlan t,
+                                 const float* __restrict__ w,
+                                 float* __restrict__ wpt) {
+  const int total = (int)(g.G * t.P * t.pstride);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += gridDim.x * blockDim.x) {
+    int e = i / t.mt;
+    const int ci = i - e * t.mt;
+    const int co = e % g.cog;
+    e /= g.cog;
+    const int slot = e % t.slots;
+    e /= t.slots;
+    wpt[i] = dc_pack_value(g, t.tmh, t.tmw, t.dqh, t.dqw, w, e / t.P, e % t.P,
+                           slot, ci, co);
+  }
+}
+
+// The top gradient's window of `ccn` channels from ch0 of image n, cells
+// from (qbh, qbw): read in row order (coalesced), written split by phase,
+// win[c][per] holding [P][LH][LW].  The operand of any (phase, tap) is then
+// unit-stride across lanes; laid out as dy is, it would be read at stride sw.
+// Zero outside the image and for the chunk's channels past ccn.
+__device__ inline void db_stage_dy(float* win, const Deconv& g,
+                                   const DbPlan& t,
+                                   const float* __restrict__ dy, int ch0,
+                                   int ccn, int n, int qbh, int qbw) {
+  const int rw = t.LW * g.sw, area = t.plane * g.sh * g.sw;
+  const int chans = g.G * g.cog;
+  for (int i = threadIdx.x; i < t.cc * area; i += kTPB) {
+    const int c = (int)fastdiv(i, t.fd_area);
+    const int rem = i - c * area;
+    const int R = (int)fastdiv(rem, t.fd_rw), Cc = rem - R * rw;
+    const int qa = (int)fastdiv(R, t.fd_sh), r = R - qa * g.sh;
+    const int qb = (int)fastdiv(Cc, t.fd_sw), s = Cc - qb * g.sw;
+    const int oh = qbh * g.sh + R, ow = qbw * g.sw + Cc;
+    float v = 0.f;
+    if (c < ccn && (unsigned)oh < (unsigned)g.OH &&
+        (unsigned)ow < (unsigned)g.OW)
+      v = dy[((n * chans + ch0 + c) * g.OH + oh) * g.OW + ow];
+    win[c * t.per + ((r * g.sw + s) * t.LH + qa) * t.LW + qb] = v;
+  }
+}
+
+// wgrad's x tile: xs[c][xst] holding [TQH][kTQW] cells of `rows` channels,
+// zero outside the image and past cn channels
+__device__ inline void db_stage_x(float* xs, const Deconv& g, const DbPlan& t,
+                                  const float* __restrict__ x, int rows,
+                                  int ch0, int cn, int n, int h0, int w0) {
+  const int chans = g.G * g.cig;
+  for (int i = threadIdx.x; i < rows * t.cells; i += kTPB) {
+    const int c = (int)fastdiv(i, t.fd_cells);
+    const int cell = i - c * t.cells;
+    const int h = h0 + cell / kTQW, w = w0 + cell % kTQW;
+    float v = 0.f;
+    if (c < cn && h < g.H && w < g.W)
+      v = x[((n * chans + ch0 + c) * g.H + h) * g.W + w];
+    xs[c * t.xst + cell] = v;
+  }
+}
+
+// window row (column) offset, under a tile's first cell, of tap 0 of the
+// phase whose forward offset is `off`: ddh - (dq - dqmin); tap t adds t
+__device__ inline int db_off(int dd, int tmax, int off) {
+  return dd + tmax - 1 - off;
+}
+
+// ---------------------------------------------------------- dgrad, direct
+// CB: input channels per thread.  A thread owns input pixels, lanes along w.
+template <int CB>
+__global__ __launch_bounds__(kTPB) void k_deconv_bwd_data_direct(
+    Deconv g, DbPlan t, const float* __restrict__ dy,
+    const float* __restrict__ wpt, float* __restrict__ dx) {
+  extern __shared__ float lds[];
+  float* win = lds;                // [cog][per]
+  float* wl = lds + t.win_floats;  // [P][slot][co][CB]
+  const DcBlock b = dc_block(g, t);
+  db_stage_dy(win, g, t, dy, b.grp * g.cog, g.cog, b.n,
+              b.q0h - t.dqh - t.ddh, b.q0w - t.dqw - t.ddw);
+  const float* wg = wpt + (long)b.grp * t.wl_floats;
+  for (int i = threadIdx.x; i < t.wl_floats; i += kTPB) wl[i] = wg[i];
+  __syncthreads();
+
+  for (int i = threadIdx.x; i < t.cells; i += kTPB) {
+    const int a = i / kTQW, bq = i % kTQW;
+    const int h = b.q0h + a, w = b.q0w + bq;
+    if (h >= g.H || w >= g.W) continue;
+    float acc[CB];
+#pragma unroll
+    for (int m = 0; m < CB; ++m) acc[m] = 0.f;
+    for (int r = 0; r < g.sh; ++r) {
+      const DcPhase fh = dc_phase(r, g.ph, g.sh, g.kh, t.tmh, t.dqh);
+      for (int s = 0; s < g.sw; ++s) {
+        const DcPhase fw = dc_phase(s, g.pw, g.sw, g.kw, t.tmw, t.dqw);
+        const int p = r * g.sw + s;
+        const float* yb = win + p * t.plane +
+                          (a + db_off(t.ddh, t.tmh, fh.off)) * t.LW + bq +
+                          db_off(t.ddw, t.tmw, fw.off);
+        const float* wb = wl + p * t.pstride;
+        for (int tt = 0; tt < fh.T; ++tt)
+          for (int u = 0; u < fw.T; ++u) {
+            const float* yp = yb + tt * t.LW + u;
+            const float* wq = wb + (tt * t.tmw + u) * g.cog * CB;
+            for (int co = 0; co < g.cog; ++co) {
+              const float v = yp[co * t.per];
+#pragma unroll
+              for (int m = 0; m < CB; ++m) acc[m] += v * wq[co * CB + m];
+            }
+          }
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < CB; ++m)
+      if (m < g.cig)
+        dx[((b.n * g.G * g.cig + b.grp * g.cig + m) * g.H + h) * g.W + w] =
+            acc[m];
+  }
+}
+
+// tap (ki, kj) of the kernel as wgrad sees it: the phase plane and the
+// window offset under a tile's first cell
+struct DbTap {
+  int p, off;  // phase; offset within the plane
+};
+__device__ inline DbTap db_tap(const Deconv& g, const DbPlan& t, int tau) {
+  const int ki = tau / g.kw, kj = tau - ki * g.kw;
+  const int r = ((ki - g.ph) % g.sh + g.sh) % g.sh;
+  const int s = ((kj - g.pw) % g.sw + g.sw) % g.sw;
+  const DcPhase fh = dc_phase(r, g.ph, g.sh, g.kh, t.tmh, t.dqh);
+  const DcPhase fw = dc_phase(s, g.pw, g.sw, g.kw, t.tmw, t.dqw);
+  return {r * g.sw + s,
+          (db_off(t.ddh, t.tmh, fh.off) + ki / g.sh) * t.LW +
+              db_off(t.ddw, t.tmw, fw.off) + kj / g.sw};
+}
+
+// the wgrad block's slice item: image and first cell
+struct DbItem {
+  int n, h0, w0;
+};
+__device__ inline DbItem db_item(const DbPlan& t, int it) {
+  const int n = it / (t.ty * t.tx), rem = it - n * (t.ty * t.tx);
+  return {n, rem / t.tx * t.TQH, rem % t.tx * kTQW};
+}
+
+// ---------------------------------------------------------- wgrad, direct
+// Threads own taps (256 of them at k16); with fewer taps than threads,
+// nsplit threads share a tap and take every nsplit-th cell, each writing a
+// partial of its own.  x is a broadcast read.  CB pads cig and cog.
+template <int CB>
+__global__ __launch_bounds__(kTPB) void k_deconv_bwd_weight_direct(
+    Deconv g, DbPlan t, const float* __restrict__ x,
+    const float* __restrict__ dy, float* __restrict__ part) {
+  extern __shared__ float lds[];
+  float* win = lds;                // [CB][per]
+  float* xs = lds + t.win_floats;  // [CB][xst]
+  const int grp = blockIdx.x % g.G, sl = blockIdx.x / g.G;
+  const int khkw = g.kh * g.kw;
+  const int js = threadIdx.x / t.tpt, tau0 = threadIdx.x - js * t.tpt;
+  const int it0 = sl * t.ipb, it1 = min(t.items, it0 + t.ipb);
+
+  for (int pass = 0; pass < t.passes; ++pass) {
+    const int tau = tau0 + pass * t.tpt;
+    const bool live = js < t.nsplit && tau < khkw;
+    const DbTap tap = db_tap(g, t, min(tau, khkw - 1));
+    float acc[CB][CB];
+#pragma unroll
+    for (int i = 0; i < CB; ++i)
+#pragma unroll
+      for (int o = 0; o < CB; ++o) acc[i][o] = 0.f;
+    for (int it = it0; it < it1; ++it) {
+      const DbItem m = db_item(t, it);
+      __syncthreads();
+      db_stage_dy(win, g, t, dy, grp * g.cog, g.cog, m.n,
+                  m.h0 - t.dqh - t.ddh, m.w0 - t.dqw - t.ddw);
+      db_stage_x(xs, g, t, x, CB, grp * g.cig, g.cig, m.n, m.h0, m.w0);
+      __syncthreads();
+      if (!live) continue;
+      const float* B = win + tap.p * t.plane + tap.off;
+      for (int cell = js; cell < t.cells; cell += t.nsplit) {
+        const float* Bc = B + cell / kTQW * t.LW + cell % kTQW;
+        float dv[CB];
+#pragma unroll
+        for (int o = 0; o < CB; ++o) dv[o] = Bc[o * t.per];
+#pragma unroll
+        for (int i = 0; i < CB; ++i) {
+          const float xv = xs[i * t.xst + cell];
+#pragma unroll
+          for (int o = 0; o < CB; ++o) acc[i][o] += xv * dv[o];
+        }
+      }
+    }
+    if (!live) continue;
+    float* pb = part + ((((long)sl * t.nsplit + js) * g.G + grp) * khkw + tau) *
+                           (CB * CB);
+#pragma unroll
+    for (int i = 0; i < CB; ++i)
+#pragma unroll
+      for (int o = 0; o < CB; ++o) pb[i * CB + o] = acc[i][o];
+  }
+}
+
+// dW[g * cig + ci][co][tap] = the sum over `nsl` partial slabs
+// [g][tap][CB][CB] in slab order; pad channels are dropped
+__global__ void k_deconv_bwd_weight_reduce(Deconv g, int nsl, int CB,
+                                           const float* __restrict__ part,
+                                           float* __restrict__ dw) {
+  const int khkw = g.kh * g.kw;
+  const int slab = g.G * khkw * CB * CB;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < slab;
+       i += gridDim.x * blockDim.x) {
+    int e = i / CB;
+    const int co = i - e * CB;
+    const int ci = e % CB;
+    e /= CB;
+    const int tau = e % khkw, grp = e / khkw;
+    if (ci >= g.cig || co >= g.cog) continue;
+    float sum = 0.f;
+    for (int s = 0; s < nsl; ++s) sum += part[(long)s * slab + i];
+    dw[((grp * g.cig + ci) * g.cog + co) * khkw + tau] = sum;
+  }
+}
+
 }  // namespace
 
 bool deconv_supported(const Deconv& g) {
@@ -457,6 +804,77 @@ void deconv_fwd(hipStream_t s, const Deconv& g, const float* x,
 #undef DC_MFMA
 #undef DC_DIRECT
   kernel_trace_deconv(t.var, t.P, t.chunks, t.ty, t.tx, t.blocks);
+}
+
+bool deconv_bwd_data_supported(const Deconv& g) {
+  const DbPlan t = db_plan(g, kBwdData);
+  return t.fits && db_counts_fit(g, t);
+}
+
+bool deconv_bwd_weight_supported(const Deconv& g) {
+  const DbPlan t = db_plan(g, kBwdWeight);
+  return t.fits && db_counts_fit(g, t);
+}
+
+void deconv_bwd_data(hipStream_t s, const Deconv& g, const float* dy,
+                     const float* w, float* dx) {
+  const DbPlan t = db_plan(g, kBwdData);
+  CHECK_(t.fits) << "deconv dgrad: window does not fit the LDS tile";
+  CHECK_(db_counts_fit(g, t)) << "deconv dgrad: 2^31 elements or more";
+  const double nx = (double)g.N * g.G * g.cig * g.H * g.W;
+  const double ny = (double)g.N * g.G * g.cog * g.OH * g.OW;
+  const double nw = (double)g.G * g.cig * g.cog * g.kh * g.kw;
+  PerfScope perf(PERF_CLASS("deconv_bwd_data"), s,
+                 2.0 * nx * g.cog * g.kh * g.kw, 4.0 * (nx + ny + nw));
+  const long nwp = (long)g.G * t.P * t.pstride;
+  float* wpt = (float*)Workspace::get_global().get(Workspace::kDeconvWT,
+                                                   sizeof(float) * nwp);
+  hipLaunchKernelGGL(k_deconv_pack_wt,
+                     dim3((unsigned)std::min<long>((nwp + kTPB - 1) / kTPB,
+                                                   2048)),
+                     dim3(kTPB), 0, s, g, t, w, wpt);
+  const dim3 grid(t.blocks), block(kTPB);
+  const size_t lds = sizeof(float) * ((size_t)t.win_floats + t.wl_floats);
+#define DB_DIRECT(CB)                                                       \
+  hipLaunchKernelGGL((k_deconv_bwd_data_direct<CB>), grid, block, lds, s, g, \
+                     t, dy, wpt, dx)
+  if (t.mt == 1) DB_DIRECT(1);
+  else if (t.mt == 2) DB_DIRECT(2);
+  else DB_DIRECT(4);
+#undef DB_DIRECT
+  kernel_trace_deconv_bwd(kBwdData, t.var, t.P, t.chunks, t.ty, t.tx,
+                          t.blocks);
+}
+
+void deconv_bwd_weight(hipStream_t s, const Deconv& g, const float* x,
+                       const float* dy, float* dw) {
+  const DbPlan t = db_plan(g, kBwdWeight);
+  CHECK_(t.fits) << "deconv wgrad: window does not fit the LDS tile";
+  CHECK_(db_counts_fit(g, t)) << "deconv wgrad: 2^31 elements or more";
+  const double nx = (double)g.N * g.G * g.cig * g.H * g.W;
+  const double ny = (double)g.N * g.G * g.cog * g.OH * g.OW;
+  const double nw = (double)g.G * g.cig * g.cog * g.kh * g.kw;
+  PerfScope perf(PERF_CLASS("deconv_bwd_weight"), s,
+                 2.0 * nx * g.cog * g.kh * g.kw, 4.0 * (nx + ny + nw));
+  float* part = (float*)Workspace::get_global().get(
+      Workspace::kDeconvPart, sizeof(float) * t.part_floats);
+  const dim3 grid(t.blocks), block(kTPB);
+  const size_t lds = sizeof(float) * ((size_t)t.win_floats + t.x_floats);
+#define DB_DIRECT(CB)                                                      \
+  hipLaunchKernelGGL((k_deconv_bwd_weight_direct<CB>), grid, block, lds, s, \
+                     g, t, x, dy, part)
+  if (t.mt == 1) DB_DIRECT(1);
+  else if (t.mt == 2) DB_DIRECT(2);
+  else DB_DIRECT(4);
+#undef DB_DIRECT
+  const int nsl = t.slices * t.nsplit;
+  const long slab = t.part_floats / nsl;
+  hipLaunchKernelGGL(k_deconv_bwd_weight_reduce,
+                     dim3((unsigned)std::min<long>((slab + kTPB - 1) / kTPB,
+                                                   2048)),
+                     dim3(kTPB), 0, s, g, nsl, t.mt, part, dw);
+  kernel_trace_deconv_bwd(kBwdWeight, t.var, t.P, t.ipb, t.slices, 0,
+                          t.blocks);
 }
 
 }  // namespace gpu

@@ -40,7 +40,7 @@ enum KOp {
   kSigmoidFwd, kSigmoidBwd, kSigmoidCeFwd, kSigmoidCeBwd, kEuclidFwd,
   kEuclidBwd, kSharedDiffSum, kContrastiveFwd, kContrastiveBwd, kGradSumsq,
   kClipFinal, kDwFwd, kDwBwdData, kDwBwdWeight, kGcFwd, kGcBwdData,
-  kGcBwdWeight, kDeconvFwd
+  kGcBwdWeight, kDeconvFwd, kDeconvBwdData, kDeconvBwdWeight
 };
 enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
             kVarScalar, kVarRing5, kVarRowThread, kVarRowWave };
@@ -88,6 +88,16 @@ void kernel_trace_deconv(int var, long phases, long chunks, long tiles_y,
                                      0, 0, 0, (unsigned char)kDeconvFwd,
                                      (unsigned char)var});
 }
+void kernel_trace_deconv_bwd(int which, int var, long phases, long chunks,
+                             long c, long d, long blocks) {
+  if (!g_ktrace_on.load(std::memory_order_relaxed)) return;
+  std::lock_guard<std::mutex> lk(g_ktrace_mu);
+  if (g_ktrace_log.size() < kKTraceCap)
+    g_ktrace_log.push_back(
+        KernelRec{phases, chunks, c, d, blocks, 0, 0, 0,
+                  (unsigned char)(kDeconvBwdData + which),
+                  (unsigned char)var});
+}
 void kernel_trace(bool enable) {
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   if (enable) {
@@ -106,7 +116,8 @@ long kernel_trace_read(char* buf, long cap) {
       "euclid_bwd",   "shared_diff_sum", "contrastive_fwd",
       "contrastive_bwd", "grad_sumsq",  "clip_final", "dwconv_fwd",
       "dwconv_bwd_data", "dwconv_bwd_weight", "gconv_fwd",
-      "gconv_bwd_data", "gconv_bwd_weight", "deconv_fwd"};
+      "gconv_bwd_data", "gconv_bwd_weight", "deconv_fwd",
+      "deconv_bwd_data", "deconv_bwd_weight"};
   // the depthwise and grouped ops keep kind * 2 + tiled in the var byte
   static const char* const dwvar[] = {"k3s1_plane", "k3s1_tile",
                                       "k3s2_plane", "k3s2_tile",
@@ -215,11 +226,18 @@ long kernel_trace_read(char* buf, long cap) {
                      r.f, r.g, r.h);
         break;
       case kDeconvFwd:
+      case kDeconvBwdData:
         n = snprintf(line, sizeof(line),
                      "op=%s var=%s phases=%ld chunks=%ld tiles_y=%ld "
                      "tiles_x=%ld blocks=%ld\n",
                      op[r.op], r.var ? "direct" : "mfma", r.a, r.b, r.c, r.d,
                      r.e);
+        break;
+      case kDeconvBwdWeight:
+        n = snprintf(line, sizeof(line),
+                     "op=%s var=%s phases=%ld chunks=%ld slices=%ld "
+                     "blocks=%ld\n",
+                     op[r.op], r.var ? "direct" : "mfma", r.a, r.b, r.c, r.e);
         break;
       default:  // sgd_seg; d as for solver_seg
         n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld%s\n",

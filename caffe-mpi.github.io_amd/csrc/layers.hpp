@@ -149,6 +149,8 @@ struct Workspace {
     kDwPart,    // dwconv_bwd_weight(): per-(channel, slice) double partials
     kGcPart,    // gconv_bwd_weight(): per-(group, slice) double partials
     kDeconvW,   // deconv_fwd(): the weights re-laid phase-major
+    kDeconvWT,  // deconv_bwd_data(): likewise, input channel innermost
+    kDeconvPart,  // deconv_bwd_weight(): per-slice partial dW tiles
     kNumSlots
   };
   void* get(Slot slot, size_t bytes);  // device (GPU mode) / host (CPU mode)
@@ -267,8 +269,13 @@ class DeconvolutionLayer : public Layer {
   // GPU forward: the phase-split kernel of kernels/deconv.hip, or dcol =
   // Wᵀ·x, col2im and a bias pass.  Decided once per Reshape.
   bool phase_split_ = false;
+  // GPU backward, per pass: the phase-split kernels, or im2col of the top
+  // gradient into col_ and the conv GEMM loops
+  bool split_dgrad_ = false, split_wgrad_ = false;
   void plan_gpu();
-  DeviceBuf col_;  // backward: im2col of the top gradient [Cout*kh*kw][N*Spad]
+  DeviceBuf col_;  // backward GEMM route: im2col of the top gradient
+                   // [Cout*kh*kw][N*Spad]; never reserved when both passes
+                   // are phase-split
   Blob zo_;        // fallback forward: the ones of the bias pass
 };
 

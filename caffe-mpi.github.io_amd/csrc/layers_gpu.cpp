@@ -336,9 +336,16 @@ void ConvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
 // variant above; that threshold is a policy constant and has NOT been
 // measured.  Stride 1, dilation > 1 and CAFFE_DECONV=0 take the form the
 // conv dgrad's kCol2im has: dcol = Wᵀ·x per group, col2im_batched, then a
-// bias pass.  Backward is the explicit-col conv of the top gradient: one
-// im2col into col_ serves the wgrad GEMMs and, when it propagates, the
-// forward GEMMs that give dx; both are Convolution's own GEMM loops.
+// bias pass.  Backward on the same conditions (and CAFFE_DECONV_BWD not 0,
+// which switches backward alone for A/B timing) is phase-split too, one
+// flag per pass: deconv_bwd_weight (x and the top gradient's phase planes
+// from LDS, split-K partials and a fixed-order reduce) and deconv_bwd_data
+// (one accumulator set per pixel over every phase and tap); the bias
+// gradient stays bias_grad.  A pass its predicate refuses (more than 4
+// channels per group on either side, a window that does not fit LDS) keeps the explicit-col conv of the top gradient: one im2col into
+// col_ serves the wgrad GEMMs and, when it propagates, the forward GEMMs
+// that give dx; both are Convolution's own GEMM loops.  col_ is reserved
+// only when a pass that runs needs it.
 static float* zeros_ones(Blob& zo, int C);
 
 static gpu::Deconv dc_geom(const DeconvolutionLayer& l) {
@@ -352,8 +359,15 @@ void DeconvolutionLayer::plan_gpu() {
     const char* e = getenv("CAFFE_DECONV");
     return e ? atoi(e) != 0 : true;
   }();
-  phase_split_ = split_ok && dh_ == 1 && dw_ == 1 && (sh_ > 1 || sw_ > 1) &&
-                 gpu::deconv_supported(dc_geom(*this));
+  static const bool bwd_ok = [] {
+    const char* e = getenv("CAFFE_DECONV_BWD");
+    return e ? atoi(e) != 0 : true;
+  }();
+  const bool zone = split_ok && dh_ == 1 && dw_ == 1 && (sh_ > 1 || sw_ > 1);
+  const gpu::Deconv g = dc_geom(*this);
+  phase_split_ = zone && gpu::deconv_supported(g);
+  split_dgrad_ = zone && bwd_ok && gpu::deconv_bwd_data_supported(g);
+  split_wgrad_ = zone && bwd_ok && gpu::deconv_bwd_weight_supported(g);
 }
 
 // the conv from the top [N][Cout][OH][OW] to the bottom [N][C][H][W]: its
@@ -400,14 +414,25 @@ void DeconvolutionLayer::Backward_gpu(const std::vector<Blob*>& top,
   if (bias_)
     gpu::bias_grad(E.stream, dy, N_, Cout_, (long)OH_ * OW_,
                    blobs_[1]->mutable_gpu_diff());
+  const bool dgrad = prop_down[0];
   const ConvGemms c = deconv_gemms(*this);
-  float* col = (float*)col_.reserve(sizeof(float) * (size_t)group_ * c.o.col);
-  gpu::im2col_batched(E.stream, dy, N_, Cout_, OH_, OW_, kh_, kw_, ph_, pw_,
-                      sh_, sw_, dh_, dw_, H_, W_, Spad_, col);
-  // the wgrad's "dY" is the bottom data: dW[ci][co, ki, kj] = x · colᵀ
-  conv_wgrad_gemms(c, bottom[0]->gpu_data(), col, true, GemmView{},
-                   blobs_[0]->mutable_gpu_diff());
-  if (prop_down[0])
+  const float* col = nullptr;
+  if (!split_wgrad_ || (dgrad && !split_dgrad_)) {
+    col = (float*)col_.reserve(sizeof(float) * (size_t)group_ * c.o.col);
+    gpu::im2col_batched(E.stream, dy, N_, Cout_, OH_, OW_, kh_, kw_, ph_, pw_,
+                        sh_, sw_, dh_, dw_, H_, W_, Spad_, (float*)col_.p);
+  }
+  if (split_wgrad_)
+    gpu::deconv_bwd_weight(E.stream, dc_geom(*this), bottom[0]->gpu_data(),
+                           dy, blobs_[0]->mutable_gpu_diff());
+  else  // the wgrad's "dY" is the bottom data: dW[ci][co, ki, kj] = x · colᵀ
+    conv_wgrad_gemms(c, bottom[0]->gpu_data(), col, true, GemmView{},
+                     blobs_[0]->mutable_gpu_diff());
+  if (!dgrad) return;
+  if (split_dgrad_)
+    gpu::deconv_bwd_data(E.stream, dc_geom(*this), dy, blobs_[0]->gpu_data(),
+                         bottom[0]->mutable_gpu_diff());
+  else
     conv_fwd_gemms(c, blobs_[0]->gpu_data(), col, true, GemmView{},
                    nchw_scatter(Spad_, S_, C_), nullptr,
                    bottom[0]->mutable_gpu_diff());

@@ -313,6 +313,12 @@ void gemm_trace_readers(long* cursor, long* wide64);
 //   op=deconv_fwd var=mfma|direct phases=<sh*sw> chunks=<input-channel
 //       chunks per block> tiles_y=<cell tiles per plane> tiles_x=<likewise>
 //       blocks=<grid>
+//   op=deconv_bwd_data var=direct phases=<sh*sw> chunks=<output-channel
+//       chunks per block> tiles_y=<input-cell tiles per plane>
+//       tiles_x=<likewise> blocks=<grid>
+//   op=deconv_bwd_weight var=direct phases=<sh*sw> chunks=<(image,
+//       cell tile) windows a block stages per tap pass> slices=<split-K
+//       slices> blocks=<first-stage grid>
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
 // The depthwise wrappers (kernels/depthwise.hip) record into the same log:
@@ -368,6 +374,9 @@ void gconv_bwd_weight(hipStream_t s, const GConv& g, const float* x,
 // 1 direct.
 void kernel_trace_deconv(int var, long phases, long chunks, long tiles_y,
                          long tiles_x, long blocks);
+// which = 0 dgrad (c, d = tiles_y, tiles_x), 1 wgrad (c = slices)
+void kernel_trace_deconv_bwd(int which, int var, long phases, long chunks,
+                             long c, long d, long blocks);
 
 // Forward of a transposed convolution at stride > 1 and dilation 1:
 // x[N][G*cig][H][W], w[G*cig][cog][kh][kw] (the Deconvolution layer's blob),
@@ -385,6 +394,22 @@ bool deconv_supported(const Deconv& g);
 // into the kDeconvW workspace slot first
 void deconv_fwd(hipStream_t s, const Deconv& g, const float* x,
                 const float* w, const float* bias, float* y);
+// Backward of the same layer, split by phase as forward is: no col of the
+// top gradient.  false as for deconv_supported() (per pass: the windows and
+// workspace slots differ), and where a channel count per group is above 4
+// (MFMA variants for those layers measured slower than im2col + GEMMs and
+// were cut, profiles/deconv.txt); the layer then keeps im2col + GEMMs for
+// that pass
+bool deconv_bwd_data_supported(const Deconv& g);
+bool deconv_bwd_weight_supported(const Deconv& g);
+// dx overwritten, every element once; packs the weights ci-innermost into
+// the kDeconvWT workspace slot first
+void deconv_bwd_data(hipStream_t s, const Deconv& g, const float* dy,
+                     const float* w, float* dx);
+// dw overwritten; split-K partials in the kDeconvPart slot, summed in fixed
+// order by a second kernel: deterministic, no atomics
+void deconv_bwd_weight(hipStream_t s, const Deconv& g, const float* x,
+                       const float* dy, float* dw);
 
 // db[c] = Σ_n Σ_s dy[n][c][s] (deterministic)
 void bias_grad(hipStream_t s, const float* dy, int N, int C, long S,

@@ -247,7 +247,13 @@ int caffe_gemm_trace_readers(long* cursor, long* wide64);
  * prototxt, net, no entry point of its own) at stride > 1 and dilation 1
  * records "op=deconv_fwd var=mfma phases=4 chunks=1 tiles_y=1 tiles_x=1
  * blocks=2" per forward (var mfma | direct; stride phases sh*sw; input-
- * channel chunks per block; cell tiles per plane; launch grid). */
+ * channel chunks per block; cell tiles per plane; launch grid).  Its
+ * backward, where both channel counts per group are at most 4, records
+ * "op=deconv_bwd_weight var=direct phases=4 chunks=1 slices=2 blocks=42"
+ * (windows a block stages per tap pass; split-K slices; first-stage grid)
+ * and "op=deconv_bwd_data var=direct phases=4 chunks=1 tiles_y=1 tiles_x=1
+ * blocks=42" (tiles of input cells); CAFFE_DECONV_BWD=0 in the environment
+ * keeps backward on im2col + GEMMs. */
 int caffe_kernel_trace(int enable);
 int caffe_kernel_trace_read(char* buf, int cap);
 /* The graph fusions planned for a net at build time, same buffer contract

@@ -1,7 +1,12 @@
 """Forward time of Deconvolution layers: the phase-split kernels of
 kernels/deconv.hip against the GEMM + col2im form (profiles/deconv.txt).
 
-  python tools/deconv_bench.py [--repeats 3] [--iters 20]
+  python tools/deconv_bench.py [--repeats 3] [--iters 20] [--backward]
+
+With --backward an iteration is one forward and one backward, the routes are
+"split" and "bwd_gemm" (CAFFE_DECONV_BWD=0: forward stays phase-split,
+backward takes im2col + GEMMs), every perf class is reported as median
+[min..max] over the repeats, and the parent compares the routes' dx and dW.
 
 Every (shape, route) pair runs in a process of its own, the routes
 alternating shape by shape and repeat by repeat: "split" (the default
@@ -25,8 +30,9 @@ SHAPES = [(32, 256, 128, 1, 32, 4, 2, 1), (32, 128, 64, 1, 64, 2, 2, 0),
           (32, 64, 3, 1, 64, 4, 2, 1), (8, 21, 21, 21, 64, 16, 8, 4)]
 
 
-def net_text(N, Ci, Co, G, H, k, s, p):
+def net_text(N, Ci, Co, G, H, k, s, p, backward=False):
     return f"""name: "up"
+force_backward: {"true" if backward else "false"}
 layer {{ name: "input" type: "Input" top: "in0"
   input_param {{ shape {{ dim: {N} dim: {Ci} dim: {H} dim: {H} }} }} }}
 layer {{ name: "up" type: "Deconvolution" bottom: "in0" top: "out"
@@ -36,33 +42,79 @@ layer {{ name: "up" type: "Deconvolution" bottom: "in0" top: "out"
 """
 
 
-def child(shape, iters):
+def child(shape, iters, backward=False):
     sys.path.insert(0, os.path.join(REPO, "caffe-mpi.github.io_amd"))
     import numpy as np
     import caffe_amd as ca
     ca.set_mode("gpu", 0)
     ca.set_random_seed(7)
     f = tempfile.NamedTemporaryFile("w", suffix=".prototxt", delete=False)
-    f.write(net_text(*shape))
+    f.write(net_text(*shape, backward=backward))
     f.close()
     net = ca.Net.from_file(f.name)
     N, Ci, _, _, H = shape[:5]
     net.set_blob("in0", np.random.default_rng(0).standard_normal(
         (N, Ci, H, H)).astype(np.float32))
-    for _ in range(3):
+    def step():
         net.forward()
+        if backward:
+            net.backward()
+
+    if backward:
+        net.forward()
+        net.set_blob("out", np.random.default_rng(1).standard_normal(
+            np.asarray(net.blob("out")).shape).astype(np.float32), diff=True)
+    for _ in range(3):
+        step()
     ca.device_synchronize()
     ca.perf_reset()
     ca.set_perf_timing(True)
     for _ in range(iters):
-        net.forward()
+        step()
     ca.device_synchronize()
     ca.set_perf_timing(False)
     us = {k: v["ns"] / iters / 1e3 for k, v in ca.perf_snapshot().items()
           if v["ns"]}
     y = np.asarray(net.blob("out"), np.float64)
-    print(json.dumps({"us": us, "sum": float(np.abs(y).sum()),
-                      "probe": y.ravel()[::9973].tolist()}))
+    res = {"us": us, "sum": float(np.abs(y).sum()),
+           "probe": y.ravel()[::9973].tolist()}
+    if backward:
+        for key, a in (("dx", net.blob("in0", diff=True)),
+                       ("dw", net.param(0, diff=True))):
+            res[key] = np.asarray(a, np.float64).ravel()[::997].tolist()
+    print(json.dumps(res))
+
+
+def probe_diff(a, b):
+    return max(abs(u - v) for u, v in zip(a, b)) / max(map(abs, b))
+
+
+def main_backward(args):
+    for i, (N, Ci, Co, G, H, k, s, p) in enumerate(SHAPES):
+        runs = {"split": [], "bwd_gemm": []}
+        for _ in range(args.repeats):
+            for name, flag in (("split", "1"), ("bwd_gemm", "0")):
+                res = subprocess.run(
+                    [sys.executable, __file__, "--iters", str(args.iters),
+                     "--backward", "--child", str(i)],
+                    env=dict(os.environ, CAFFE_DECONV_BWD=flag), timeout=300,
+                    capture_output=True, text=True, check=True)
+                runs[name].append(json.loads(res.stdout.splitlines()[-1]))
+        a, b = runs["split"][0], runs["bwd_gemm"][0]
+        col = 4 * (Co // G) * k * k * G * N * ((H * H + 15) // 16 * 16)
+        print(f"== N={N} {Ci}->{Co} group {G} at {H}x{H} k{k} s{s} p{p}: "
+              f"col of the top gradient {col / 1e6:.0f} MB; routes differ by "
+              f"dx {probe_diff(a['dx'], b['dx']):.1e}, "
+              f"dW {probe_diff(a['dw'], b['dw']):.1e} of the largest")
+        for name, rs in runs.items():
+            bwd = [sum(v for c, v in r["us"].items() if c != "deconv_fwd")
+                   for r in rs]
+            print(f"{name:>9}: backward us {statistics.median(bwd):9.1f} "
+                  f"[{min(bwd):.1f}..{max(bwd):.1f}]")
+            for c in sorted(rs[0]["us"]):
+                v = [r["us"].get(c, 0.0) for r in rs]
+                print(f"{'':>11}{c:<20}{statistics.median(v):9.1f} "
+                      f"[{min(v):.1f}..{max(v):.1f}]", flush=True)
 
 
 def main():
@@ -70,9 +122,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--child", type=int)
+    ap.add_argument("--backward", action="store_true")
     args = ap.parse_args()
     if args.child is not None:
-        return child(SHAPES[args.child], args.iters)
+        return child(SHAPES[args.child], args.iters, args.backward)
+    if args.backward:
+        return main_backward(args)
     for i, (N, Ci, Co, G, H, k, s, p) in enumerate(SHAPES):
         runs = {"split": [], "gemm": []}
         for _ in range(args.repeats):
