@@ -289,7 +289,11 @@ def kernel_trace_read():
     per block), tiles_y, tiles_x, blocks; its backward with at most 4
     channels per group on both sides records deconv_bwd_weight with var,
     phases, chunks (windows staged per block), slices, blocks and
-    deconv_bwd_data with var, phases, chunks, tiles_y, tiles_x, blocks."""
+    deconv_bwd_data with var, phases, chunks, tiles_y, tiles_x, blocks.  A
+    SoftmaxWithLoss with a loss_param records dsm_fwd | dsm_bwd with form
+    (resident | stream), CR (padded channels held in registers, 0 when
+    streaming), P (pixels per thread), vec (floats per access), rows, C,
+    blocks."""
     return _trace_records(_lib.caffe_kernel_trace_read)
 
 

@@ -40,10 +40,12 @@ enum KOp {
   kSigmoidFwd, kSigmoidBwd, kSigmoidCeFwd, kSigmoidCeBwd, kEuclidFwd,
   kEuclidBwd, kSharedDiffSum, kContrastiveFwd, kContrastiveBwd, kGradSumsq,
   kClipFinal, kDwFwd, kDwBwdData, kDwBwdWeight, kGcFwd, kGcBwdData,
-  kGcBwdWeight, kDeconvFwd, kDeconvBwdData, kDeconvBwdWeight
+  kGcBwdWeight, kDeconvFwd, kDeconvBwdData, kDeconvBwdWeight, kDsmFwd,
+  kDsmBwd
 };
 enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
-            kVarScalar, kVarRing5, kVarRowThread, kVarRowWave };
+            kVarScalar, kVarRing5, kVarRowThread, kVarRowWave, kVarResident,
+            kVarStream };
 struct KernelRec {
   long a, b, c, d;  // per-op fields, see kernel_trace_read
   long e, f, g, h;  // the grouped-conv ops alone
@@ -98,6 +100,15 @@ void kernel_trace_deconv_bwd(int which, int var, long phases, long chunks,
                   (unsigned char)(kDeconvBwdData + which),
                   (unsigned char)var});
 }
+void kernel_trace_dsm(int which, bool stream, const long (&f)[6]) {
+  if (!g_ktrace_on.load(std::memory_order_relaxed)) return;
+  std::lock_guard<std::mutex> lk(g_ktrace_mu);
+  if (g_ktrace_log.size() < kKTraceCap)
+    g_ktrace_log.push_back(
+        KernelRec{f[0], f[1], f[2], f[3], f[4], f[5], 0, 0,
+                  (unsigned char)(kDsmFwd + which),
+                  (unsigned char)(stream ? kVarStream : kVarResident)});
+}
 void kernel_trace(bool enable) {
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   if (enable) {
@@ -117,7 +128,7 @@ long kernel_trace_read(char* buf, long cap) {
       "contrastive_bwd", "grad_sumsq",  "clip_final", "dwconv_fwd",
       "dwconv_bwd_data", "dwconv_bwd_weight", "gconv_fwd",
       "gconv_bwd_data", "gconv_bwd_weight", "deconv_fwd",
-      "deconv_bwd_data", "deconv_bwd_weight"};
+      "deconv_bwd_data", "deconv_bwd_weight", "dsm_fwd", "dsm_bwd"};
   // the depthwise and grouped ops keep kind * 2 + tiled in the var byte
   static const char* const dwvar[] = {"k3s1_plane", "k3s1_tile",
                                       "k3s2_plane", "k3s2_tile",
@@ -128,7 +139,7 @@ long kernel_trace_read(char* buf, long cap) {
   static const char* const var[] = {"",        "k3",     "k3s1",
                                     "k3s2",    "generic", "v4",
                                     "scalar",  "ring5",  "row_thread",
-                                    "row_wave"};
+                                    "row_wave", "resident", "stream"};
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   long len = 0;
   if (cap > 0) buf[0] = 0;
@@ -238,6 +249,13 @@ long kernel_trace_read(char* buf, long cap) {
                      "op=%s var=%s phases=%ld chunks=%ld slices=%ld "
                      "blocks=%ld\n",
                      op[r.op], r.var ? "direct" : "mfma", r.a, r.b, r.c, r.e);
+        break;
+      case kDsmFwd:
+      case kDsmBwd:
+        n = snprintf(line, sizeof(line),
+                     "op=%s form=%s CR=%ld P=%ld vec=%ld rows=%ld C=%ld "
+                     "blocks=%ld\n",
+                     op[r.op], var[r.var], r.a, r.b, r.c, r.d, r.e, r.f);
         break;
       default:  // sgd_seg; d as for solver_seg
         n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld%s\n",

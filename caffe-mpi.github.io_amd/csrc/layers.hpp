@@ -614,6 +614,18 @@ class SoftmaxWithLossLayer : public Layer {
   bool is_loss_layer() const override { return true; }
   int outer_ = 0, C_ = 0, inner_ = 0;
   Blob prob_;
+  // loss_param (reference softmax_loss_layer.cpp:29-41).  A layer that has
+  // the block reads ignore_label / normalization and, in GPU mode, runs the
+  // pixel-major kernels of kernels/dense_softmax.hip at any shape; a layer
+  // without one keeps the class-per-row launches and divides by outer*inner.
+  bool dense_ = false;
+  bool has_ignore_ = false;
+  int ignore_ = 0;
+  int norm_ = kNormValid;  // LossNorm
+  DeviceBuf norm_slot_;    // GPU mode: {valid count, 1 / normalizer}
+  gpu::DenseSoftmax dense_geom() const {
+    return gpu::DenseSoftmax{outer_, C_, inner_, has_ignore_, ignore_, norm_};
+  }
 };
 
 // Sigmoid (reference layers/sigmoid_layer.cpp/.cu): y = 1 / (1 + exp(-x)),
@@ -730,6 +742,29 @@ class SliceLayer : public Layer {
   std::vector<int> points_;  // slice_point
   int outer_ = 0, C_ = 0;    // bottom as [outer_][C_][inner_]
   long inner_ = 0;
+};
+
+// Crop (reference layers/crop_layer.cpp): the top is the window of bottom 0
+// that has bottom 1's sizes from `axis` on, starting at `offset` (none = 0,
+// one = every cropped axis, or one per cropped axis).  Bottom 1 gives sizes
+// only and never takes a gradient; bottom 0's diff is the top diff inside
+// the window and zero outside, written in one pass.  Neighbouring axes that
+// are not cropped are merged, which leaves at most four (gpu::CropGeom).
+class CropLayer : public Layer {
+ public:
+  using Layer::Layer;
+  int min_bottom_blobs() const override { return 2; }
+  int max_bottom_blobs() const override { return 2; }
+  void Reshape(const std::vector<Blob*>&, const std::vector<Blob*>&) override;
+  void Forward_cpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Forward_gpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Backward_cpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  gpu::CropGeom geom_{};
 };
 
 // Flatten (reference layers/flatten_layer.cpp): axes [axis, end_axis]

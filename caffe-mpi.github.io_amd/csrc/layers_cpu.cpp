@@ -1146,7 +1146,26 @@ void SoftmaxLayer::Backward_cpu(const std::vector<Blob*>& top,
 
 // ---------------------------------------------------------- SoftmaxWithLoss
 void SoftmaxWithLossLayer::LayerSetUp(const std::vector<Blob*>&,
-                                      const std::vector<Blob*>&) {}
+                                      const std::vector<Blob*>&) {
+  auto lp = param_->sub("loss_param");
+  dense_ = lp != nullptr;
+  if (!lp) return;
+  has_ignore_ = lp->has("ignore_label");
+  ignore_ = (int)lp->inum("ignore_label");
+  // the deprecated bool counts only where normalization is absent
+  norm_ = kNormValid;
+  if (lp->has("normalization")) {
+    static const char* const names[] = {"FULL", "VALID", "BATCH_SIZE", "NONE"};
+    const std::string n = lp->str("normalization");
+    norm_ = -1;
+    for (int i = 0; i < 4; ++i)
+      if (n == names[i]) norm_ = i;
+    CHECK_(norm_ >= 0) << "SoftmaxWithLoss layer '" << name()
+                       << "': unknown normalization '" << n << "'";
+  } else if (lp->has("normalize")) {
+    norm_ = lp->boolean("normalize") ? kNormValid : kNormBatchSize;
+  }
+}
 
 void SoftmaxWithLossLayer::Reshape(const std::vector<Blob*>& bottom,
                                    const std::vector<Blob*>& top) {
@@ -1160,12 +1179,43 @@ void SoftmaxWithLossLayer::Reshape(const std::vector<Blob*>& bottom,
   top[0]->Reshape({1});
 }
 
+// loss_param form: the sum of softmax_nll_term over the non-ignored pixels
+// and their count; a non-ignored label outside [0, C) is an error here (the
+// GPU kernels, which cannot raise, give a NaN loss)
+static double dense_loss_cpu(const SoftmaxWithLossLayer& L, const float* prob,
+                             const float* label, long* valid) {
+  double loss = 0;
+  long n = 0;
+  for (int o = 0; o < L.outer_; ++o)
+    for (int s = 0; s < L.inner_; ++s) {
+      const int lv = (int)label[(long)o * L.inner_ + s];
+      if (L.has_ignore_ && lv == L.ignore_) continue;
+      CHECK_(lv >= 0 && lv < L.C_)
+          << "SoftmaxWithLoss layer '" << L.name() << "': label " << lv
+          << " at image " << o << ", pixel " << s << " is outside [0, "
+          << L.C_ << ")";
+      ++n;
+      if (prob)
+        loss += (double)softmax_nll_term(
+            prob[((long)o * L.C_ + lv) * L.inner_ + s]);
+    }
+  *valid = n;
+  return loss;
+}
+
 void SoftmaxWithLossLayer::Forward_cpu(const std::vector<Blob*>& bottom,
                                        const std::vector<Blob*>& top) {
   softmax_cpu_impl(bottom[0]->cpu_data(), outer_, C_, inner_,
                    prob_.mutable_cpu_data());
   const float* prob = prob_.cpu_data();
   const float* label = bottom[1]->cpu_data();
+  if (dense_) {
+    long valid = 0;
+    const double sum = dense_loss_cpu(*this, prob, label, &valid);
+    top[0]->mutable_cpu_data()[0] = (float)(
+        sum / softmax_loss_normalizer(norm_, outer_, inner_, valid));
+    return;
+  }
   double loss = 0;
   for (int o = 0; o < outer_; ++o)
     for (int s = 0; s < inner_; ++s) {
@@ -1187,6 +1237,24 @@ void SoftmaxWithLossLayer::Backward_cpu(const std::vector<Blob*>& top,
   const float* label = bottom[1]->cpu_data();
   float* dx = bottom[0]->mutable_cpu_diff();
   const long n = (long)outer_ * C_ * inner_;
+  if (dense_) {
+    long valid = 0;
+    dense_loss_cpu(*this, nullptr, label, &valid);
+    // the scale as the GPU finalizer rounds it
+    const float scale =
+        lw * (float)(1.0 / softmax_loss_normalizer(norm_, outer_, inner_,
+                                                   valid));
+    for (int o = 0; o < outer_; ++o)
+      for (int s = 0; s < inner_; ++s) {
+        const int lv = (int)label[(long)o * inner_ + s];
+        const bool keep = !(has_ignore_ && lv == ignore_);
+        for (int c = 0; c < C_; ++c) {
+          const long i = ((long)o * C_ + c) * inner_ + s;
+          dx[i] = keep ? (prob[i] - (c == lv ? 1.f : 0.f)) * scale : 0.f;
+        }
+      }
+    return;
+  }
   memcpy(dx, prob, sizeof(float) * n);
   for (int o = 0; o < outer_; ++o)
     for (int s = 0; s < inner_; ++s) {
@@ -1514,6 +1582,93 @@ void SliceLayer::Backward_cpu(const std::vector<Blob*>& top,
   }
 }
 
+// ----------------------------------------------------------------- Crop
+void CropLayer::Reshape(const std::vector<Blob*>& bottom,
+                        const std::vector<Blob*>& top) {
+  auto cp = param_->sub("crop_param");
+  const int axes = bottom[0]->num_axes();
+  int axis = cp ? (int)cp->inum("axis", 2) : 2;
+  CHECK_(axis >= -axes && axis < axes)
+      << "Crop layer '" << name() << "': axis " << axis
+      << " out of range for a " << axes << "-axis bottom";
+  if (axis < 0) axis += axes;
+  CHECK_EQ_(bottom[1]->num_axes(), axes)
+      << "Crop layer '" << name() << "': both bottoms need " << axes
+      << " axes";
+  CHECK_(top[0] != bottom[0] && top[0] != bottom[1])
+      << "Crop layer '" << name() << "' does not run in-place";
+  const std::vector<long> offs =
+      cp ? cp->inums("offset") : std::vector<long>();
+  CHECK_(offs.size() <= 1 || (int)offs.size() == axes - axis)
+      << "Crop layer '" << name() << "': " << offs.size()
+      << " offset values for " << axes - axis
+      << " cropped axes (none, one, or one per axis from " << axis << " on)";
+  // per axis (bottom size, window size, offset), an uncropped axis merged
+  // into the one before it
+  std::vector<std::array<long, 3>> dims;
+  std::vector<int> shape = bottom[0]->shape();
+  for (int i = 0; i < axes; ++i) {
+    const long B = bottom[0]->shape(i);
+    long T = B, off = 0;
+    if (i >= axis) {
+      T = bottom[1]->shape(i);
+      off = offs.empty() ? 0 : offs.size() == 1 ? offs[0] : offs[i - axis];
+      CHECK_(off >= 0 && off + T <= B)
+          << "Crop layer '" << name() << "': the window of size " << T
+          << " at offset " << off << " leaves axis " << i << " of size " << B;
+    }
+    shape[i] = (int)T;
+    if (!dims.empty() && T == B) {
+      for (long& v : dims.back()) v *= B;
+    } else {
+      dims.push_back({B, T, off});
+    }
+  }
+  CHECK_LE_((int)dims.size(), 4)
+      << "Crop layer '" << name() << "': more than four cropped axes";
+  CHECK_(bottom[0]->count() < (1L << 31))
+      << "Crop layer '" << name() << "': bottom of 2^31 elements or more";
+  const size_t lead = 4 - dims.size();
+  for (size_t k = 0; k < 4; ++k) {
+    geom_.B[k] = k < lead ? 1u : (unsigned)dims[k - lead][0];
+    geom_.T[k] = k < lead ? 1u : (unsigned)dims[k - lead][1];
+    geom_.off[k] = k < lead ? 0u : (unsigned)dims[k - lead][2];
+  }
+  if (top[0]->shape() != shape) top[0]->Reshape(shape);
+}
+
+// calls f(bottom offset, top offset) for every innermost run of the window
+template <class F>
+static void crop_rows(const gpu::CropGeom& g, F f) {
+  for (unsigned a = 0; a < g.T[0]; ++a)
+    for (unsigned b = 0; b < g.T[1]; ++b)
+      for (unsigned c = 0; c < g.T[2]; ++c)
+        f((((long)(a + g.off[0]) * g.B[1] + b + g.off[1]) * g.B[2] + c +
+           g.off[2]) * g.B[3] + g.off[3],
+          (((long)a * g.T[1] + b) * g.T[2] + c) * g.T[3]);
+}
+
+void CropLayer::Forward_cpu(const std::vector<Blob*>& bottom,
+                            const std::vector<Blob*>& top) {
+  const float* x = bottom[0]->cpu_data();
+  float* y = top[0]->mutable_cpu_data();
+  crop_rows(geom_, [&](long src, long dst) {
+    memcpy(y + dst, x + src, sizeof(float) * geom_.T[3]);
+  });
+}
+
+void CropLayer::Backward_cpu(const std::vector<Blob*>& top,
+                             const std::vector<bool>& prop_down,
+                             const std::vector<Blob*>& bottom) {
+  if (!prop_down[0]) return;
+  const float* dy = top[0]->cpu_diff();
+  float* dx = bottom[0]->mutable_cpu_diff();
+  memset(dx, 0, sizeof(float) * bottom[0]->count());
+  crop_rows(geom_, [&](long src, long dst) {
+    memcpy(dx + src, dy + dst, sizeof(float) * geom_.T[3]);
+  });
+}
+
 // ---------------------------------------------------------------- Flatten
 void FlattenLayer::Reshape(const std::vector<Blob*>& bottom,
                            const std::vector<Blob*>& top) {
@@ -1583,6 +1738,7 @@ REGISTER_LAYER("EuclideanLoss", EuclideanLossLayer)
 REGISTER_LAYER("Flatten", FlattenLayer)
 REGISTER_LAYER("ContrastiveLoss", ContrastiveLossLayer)
 REGISTER_LAYER("Slice", SliceLayer)
+REGISTER_LAYER("Crop", CropLayer)
 // ---------------------------------------------------------------- Scale
 // Reference layers/scale_layer.cpp (+ bias inside, :121-134): channel-wise
 // y = x * scale[c] (+ bias[c]); the BVLC BatchNorm+Scale prototxt pattern.

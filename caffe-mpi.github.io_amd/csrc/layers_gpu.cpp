@@ -817,6 +817,16 @@ void SoftmaxLayer::Forward_gpu(const std::vector<Blob*>& bottom,
 void SoftmaxWithLossLayer::Forward_gpu(const std::vector<Blob*>& bottom,
                                        const std::vector<Blob*>& top) {
   Engine& E = Engine::get();
+  if (dense_) {
+    gpu::dense_softmaxloss_fwd(
+        E.stream, dense_geom(), bottom[0]->gpu_data(), bottom[1]->gpu_data(),
+        prob_.mutable_gpu_data(),
+        (double*)Workspace::get_global().get(
+            Workspace::kLossPart, sizeof(double) * gpu::kDsmPartials),
+        top[0]->mutable_gpu_data(),
+        (float*)norm_slot_.reserve(2 * sizeof(float)));
+    return;
+  }
   gpu::softmax_fwd(E.stream, bottom[0]->gpu_data(), outer_, C_, inner_,
                    prob_.mutable_gpu_data());
   gpu::softmaxloss_fwd(E.stream, prob_.gpu_data(), bottom[1]->gpu_data(),
@@ -827,11 +837,34 @@ void SoftmaxWithLossLayer::Backward_gpu(const std::vector<Blob*>& top,
                                         const std::vector<bool>& prop_down,
                                         const std::vector<Blob*>& bottom) {
   if (!prop_down[0]) return;
+  if (dense_) {
+    CHECK_GE_(norm_slot_.bytes, 2 * sizeof(float)) << "Backward before Forward";
+    gpu::dense_softmaxloss_bwd(
+        Engine::get().stream, dense_geom(), prob_.gpu_data(),
+        bottom[1]->gpu_data(), (const float*)norm_slot_.p, loss(0),
+        bottom[0]->mutable_gpu_diff());
+    return;
+  }
   const float scale = loss(0) / ((float)outer_ * inner_);
   gpu::softmaxloss_bwd(Engine::get().stream, prob_.gpu_data(),
                        bottom[1]->gpu_data(), outer_, C_, inner_, scale,
                        bottom[0]->mutable_gpu_diff());
   (void)top;
+}
+
+// ------------------------------------------------------------------- Crop
+void CropLayer::Forward_gpu(const std::vector<Blob*>& bottom,
+                            const std::vector<Blob*>& top) {
+  gpu::crop_fwd(Engine::get().stream, geom_, bottom[0]->gpu_data(),
+                top[0]->mutable_gpu_data());
+}
+
+void CropLayer::Backward_gpu(const std::vector<Blob*>& top,
+                             const std::vector<bool>& prop_down,
+                             const std::vector<Blob*>& bottom) {
+  if (!prop_down[0]) return;
+  gpu::crop_bwd(Engine::get().stream, geom_, top[0]->gpu_diff(),
+                bottom[0]->mutable_gpu_diff());
 }
 
 // ---------------------------------------------------------------- Sigmoid

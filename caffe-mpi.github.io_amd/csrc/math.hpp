@@ -153,6 +153,29 @@ CAMD_HD inline float contrastive_row_beta(float dsq, bool similar,
   return mdist > 0.f ? -alpha * mdist / (d + 1e-4f) : 0.f;
 }
 
+// ------------------------------------------------- softmax loss, loss_param
+// Per-pixel formulas of the reference's softmax_loss_layer.cpp:65-117 for a
+// SoftmaxWithLoss layer that carries a loss_param, shared by the CPU loop
+// and the dense kernels (kernels/dense_softmax.hip).
+enum LossNorm { kNormFull = 0, kNormValid, kNormBatchSize, kNormNone };
+// the term the loss SUMS for a pixel whose label has probability p.  The
+// clamp is a comparison, not fmaxf (which drops a NaN operand): a NaN p is
+// returned as it is, so a contaminated row gives a NaN loss in both modes.
+CAMD_HD inline float softmax_nll_term(float p) {
+  if (p != p) return p;
+  return -logf(p < 1.175494351e-38f ? 1.175494351e-38f : p);
+}
+// max(1, .) of the count the mode names; valid = the non-ignored labels
+// (equal to outer * inner when the layer has no ignore_label)
+CAMD_HD inline double softmax_loss_normalizer(int mode, long outer,
+                                              long inner, long valid) {
+  double n = 1.0;
+  if (mode == kNormFull) n = (double)(outer * inner);
+  if (mode == kNormValid) n = (double)valid;
+  if (mode == kNormBatchSize) n = (double)outer;
+  return n < 1.0 ? 1.0 : n;
+}
+
 // ------------------------------------------------------ data feed transform
 // One output value of the uint8 crop/mirror/mean/scale transform (the
 // reference's DataTransformer::Transform): im is one record [C][inH][inW],
@@ -319,6 +342,9 @@ void gemm_trace_readers(long* cursor, long* wide64);
 //   op=deconv_bwd_weight var=direct phases=<sh*sw> chunks=<(image,
 //       cell tile) windows a block stages per tap pass> slices=<split-K
 //       slices> blocks=<first-stage grid>
+//   op=dsm_fwd|dsm_bwd form=resident|stream CR=<padded channels held in
+//       registers; 0 when streaming> P=<pixels per thread> vec=<floats per
+//       access> rows=<outer*inner> C=<C> blocks=<grid>
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
 // The depthwise wrappers (kernels/depthwise.hip) record into the same log:
@@ -498,6 +524,47 @@ void softmaxloss_fwd(hipStream_t s, const float* prob, const float* label,
                      int outer, int C, int inner, float* loss_out);
 void softmaxloss_bwd(hipStream_t s, const float* prob, const float* label,
                      int outer, int C, int inner, float scale, float* dx);
+
+// SoftmaxWithLoss with a loss_param, pixel-major (kernels/dense_softmax.hip):
+// x, prob, dx [outer][C][inner], label [outer][inner].  A thread owns P
+// pixels adjacent along inner and walks the channels, so every access is
+// unit-stride across lanes; C <= 32 keeps the logits in registers
+// (resident), wider rows stream x twice.  The forward writes prob once,
+// sums softmax_nll_term over the non-ignored pixels (a non-ignored label
+// outside [0, C) adds NaN and is never an index) into `partials`
+// (kDsmPartials doubles, fixed grid, no atomics), and one block then writes
+// loss_out[0] = sum / normalizer and norm_slot = {valid count,
+// 1 / normalizer}.  The backward reads the scale from norm_slot[1], so no
+// mode needs a host read-back: dx = (prob - onehot) * loss_weight *
+// norm_slot[1], exact zeros at ignored pixels, every element written once.
+struct DenseSoftmax {
+  int outer, C, inner;
+  bool has_ignore;
+  int ignore;
+  int norm;  // LossNorm
+};
+constexpr int kDsmMaxBlocks = 1024;  // grid cap; grid-stride beyond it
+constexpr int kDsmPartials = 2 * kDsmMaxBlocks;
+void dense_softmaxloss_fwd(hipStream_t s, const DenseSoftmax& g,
+                           const float* x, const float* label, float* prob,
+                           double* partials, float* loss_out,
+                           float* norm_slot);
+void dense_softmaxloss_bwd(hipStream_t s, const DenseSoftmax& g,
+                           const float* prob, const float* label,
+                           const float* norm_slot, float loss_weight,
+                           float* dx);
+// records op=dsm_fwd|dsm_bwd (which = 0 | 1); f = CR, P, vec, rows, C, blocks
+void kernel_trace_dsm(int which, bool stream, const long (&f)[6]);
+
+// Crop: a window of x copied into y (forward), or dy laid into a zero dx
+// (backward, every dx element written once), over at most four collapsed
+// axes: B the bottom's sizes, T the window's, off its start; axis 3 is the
+// innermost, where lanes run.  Each tensor has fewer than 2^31 elements.
+struct CropGeom {
+  unsigned B[4], T[4], off[4];
+};
+void crop_fwd(hipStream_t s, const CropGeom& g, const float* x, float* y);
+void crop_bwd(hipStream_t s, const CropGeom& g, const float* dy, float* dx);
 
 // Sigmoid (sigmoid_layer.cu): y = 1 / (1 + exp(-x)), x == y allowed;
 // dx = dy * y * (1 - y) from the TOP data, so in-place needs no saved input.
