@@ -293,7 +293,9 @@ def kernel_trace_read():
     SoftmaxWithLoss with a loss_param records dsm_fwd | dsm_bwd with form
     (resident | stream), CR (padded channels held in registers, 0 when
     streaming), P (pixels per thread), vec (floats per access), rows, C,
-    blocks."""
+    blocks.  An LRN with norm_region WITHIN_CHANNEL records lrn_within_fwd |
+    lrn_within_bwd with var (k3 | generic), split (planes | tiles),
+    planes (per block), tiles_y, tiles_x, blocks."""
     return _trace_records(_lib.caffe_kernel_trace_read)
 
 

@@ -41,7 +41,7 @@ enum KOp {
   kEuclidBwd, kSharedDiffSum, kContrastiveFwd, kContrastiveBwd, kGradSumsq,
   kClipFinal, kDwFwd, kDwBwdData, kDwBwdWeight, kGcFwd, kGcBwdData,
   kGcBwdWeight, kDeconvFwd, kDeconvBwdData, kDeconvBwdWeight, kDsmFwd,
-  kDsmBwd
+  kDsmBwd, kLrnWithinFwd, kLrnWithinBwd
 };
 enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
             kVarScalar, kVarRing5, kVarRowThread, kVarRowWave, kVarResident,
@@ -109,6 +109,16 @@ void kernel_trace_dsm(int which, bool stream, const long (&f)[6]) {
                   (unsigned char)(kDsmFwd + which),
                   (unsigned char)(stream ? kVarStream : kVarResident)});
 }
+void kernel_trace_lrn_within(int which, int var, bool tiled, long planes,
+                             long tiles_y, long tiles_x, long blocks) {
+  if (!g_ktrace_on.load(std::memory_order_relaxed)) return;
+  std::lock_guard<std::mutex> lk(g_ktrace_mu);
+  if (g_ktrace_log.size() < kKTraceCap)
+    g_ktrace_log.push_back(
+        KernelRec{planes, tiles_y, tiles_x, blocks, tiled, 0, 0, 0,
+                  (unsigned char)(kLrnWithinFwd + which),
+                  (unsigned char)(var ? kVarGeneric : kVarK3)});
+}
 void kernel_trace(bool enable) {
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   if (enable) {
@@ -128,7 +138,8 @@ long kernel_trace_read(char* buf, long cap) {
       "contrastive_bwd", "grad_sumsq",  "clip_final", "dwconv_fwd",
       "dwconv_bwd_data", "dwconv_bwd_weight", "gconv_fwd",
       "gconv_bwd_data", "gconv_bwd_weight", "deconv_fwd",
-      "deconv_bwd_data", "deconv_bwd_weight", "dsm_fwd", "dsm_bwd"};
+      "deconv_bwd_data", "deconv_bwd_weight", "dsm_fwd", "dsm_bwd",
+      "lrn_within_fwd", "lrn_within_bwd"};
   // the depthwise and grouped ops keep kind * 2 + tiled in the var byte
   static const char* const dwvar[] = {"k3s1_plane", "k3s1_tile",
                                       "k3s2_plane", "k3s2_tile",
@@ -256,6 +267,14 @@ long kernel_trace_read(char* buf, long cap) {
                      "op=%s form=%s CR=%ld P=%ld vec=%ld rows=%ld C=%ld "
                      "blocks=%ld\n",
                      op[r.op], var[r.var], r.a, r.b, r.c, r.d, r.e, r.f);
+        break;
+      case kLrnWithinFwd:
+      case kLrnWithinBwd:
+        n = snprintf(line, sizeof(line),
+                     "op=%s var=%s split=%s planes=%ld tiles_y=%ld "
+                     "tiles_x=%ld blocks=%ld\n",
+                     op[r.op], var[r.var], r.e ? "tiles" : "planes", r.a, r.b,
+                     r.c, r.d);
         break;
       default:  // sgd_seg; d as for solver_seg
         n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld%s\n",

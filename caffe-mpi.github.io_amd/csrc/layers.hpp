@@ -493,11 +493,8 @@ class LRNLayer : public Layer {
   using Layer::Layer;
   void LayerSetUp(const std::vector<Blob*>&,
                   const std::vector<Blob*>&) override;
-  void Reshape(const std::vector<Blob*>& b,
-               const std::vector<Blob*>& t) override {
-    t[0]->ReshapeLike(*b[0]);
-    scale_.ReshapeLike(*b[0]);
-  }
+  void Reshape(const std::vector<Blob*>&,
+               const std::vector<Blob*>&) override;
   void Forward_cpu(const std::vector<Blob*>&,
                    const std::vector<Blob*>&) override;
   void Forward_gpu(const std::vector<Blob*>&,
@@ -506,9 +503,16 @@ class LRNLayer : public Layer {
                     const std::vector<Blob*>&) override;
   void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
                     const std::vector<Blob*>&) override;
+  void Forward_within_cpu(Blob& bottom, Blob& top);
+  void Backward_within_cpu(Blob& top, Blob& bottom);
   int size_ = 5;
   float alpha_ = 1.f, beta_ = 0.75f, k_ = 1.f;
-  Blob scale_;
+  Blob scale_;  // the denominator's base: k + ..., or 1 + ... when within_
+  // norm_region WITHIN_CHANNEL: a size x size window of the element's own
+  // plane; geometry and the GPU work split are set once per Reshape
+  bool within_ = false;
+  gpu::LrnWithin within_geom_{};
+  gpu::LrnWithinPlan within_plan_{};
 };
 
 class DropoutLayer : public Layer {

@@ -867,8 +867,8 @@ void EltwiseLayer::Backward_cpu(const std::vector<Blob*>& top,
 }
 
 // ---------------------------------------------------------------- LRN
-void LRNLayer::LayerSetUp(const std::vector<Blob*>&,
-                          const std::vector<Blob*>&) {
+void LRNLayer::LayerSetUp(const std::vector<Blob*>& bottom,
+                          const std::vector<Blob*>& top) {
   auto lp = param_->sub("lrn_param");
   size_ = lp ? (int)lp->inum("local_size", 5) : 5;
   CHECK_EQ_(size_ % 2, 1);
@@ -877,11 +877,99 @@ void LRNLayer::LayerSetUp(const std::vector<Blob*>&,
   k_ = lp ? (float)lp->num("k", 1.0) : 1.f;
   const std::string region =
       lp ? lp->str("norm_region", "ACROSS_CHANNELS") : "ACROSS_CHANNELS";
-  CHECK_(region == "ACROSS_CHANNELS");
+  CHECK_(region == "ACROSS_CHANNELS" || region == "WITHIN_CHANNEL")
+      << "LRN layer '" << name() << "': norm_region '" << region << "'";
+  within_ = region == "WITHIN_CHANNEL";
+  if (!within_) return;
+  CHECK_(top[0] != bottom[0])
+      << "LRN layer '" << name()
+      << "' with norm_region WITHIN_CHANNEL does not run in-place";
+  CHECK_(size_ <= gpu::kLrnWithinMaxSize)
+      << "LRN layer '" << name() << "': local_size " << size_
+      << " is above " << gpu::kLrnWithinMaxSize
+      << ", the largest a WITHIN_CHANNEL window may have";
+}
+
+void LRNLayer::Reshape(const std::vector<Blob*>& bottom,
+                       const std::vector<Blob*>& top) {
+  top[0]->ReshapeLike(*bottom[0]);
+  scale_.ReshapeLike(*bottom[0]);
+  if (!within_) return;
+  CHECK_EQ_(bottom[0]->num_axes(), 4)
+      << "LRN layer '" << name() << "': WITHIN_CHANNEL needs a 4-D bottom";
+  within_geom_ = {bottom[0]->num() * bottom[0]->channels(),
+                  bottom[0]->height(), bottom[0]->width(), size_, alpha_,
+                  beta_};
+  within_plan_ = gpu::lrn_within_plan(within_geom_);
+}
+
+// WITHIN_CHANNEL: s = 1 + alpha / size^2 * Σ_window x^2 over the size x size
+// window of the element's own plane, zero outside it (lrn_layer.cpp:17-65:
+// the AVE pool of stride 1 and pad pre divides by size^2 at the border too);
+// lrn_param.k is not used
+template <typename F>
+static float window_sum(int H, int W, int pre, int h, int w, F f) {
+  float acc = 0;
+  for (int hh = std::max(0, h - pre); hh <= std::min(H - 1, h + pre); ++hh)
+    for (int ww = std::max(0, w - pre); ww <= std::min(W - 1, w + pre); ++ww)
+      acc += f(hh * W + ww);
+  return acc;
+}
+
+void LRNLayer::Forward_within_cpu(Blob& bottom, Blob& top) {
+  const gpu::LrnWithin& g = within_geom_;
+  const int pre = (size_ - 1) / 2, S = g.H * g.W;
+  const float aos = alpha_ / (size_ * size_);
+  const float* x = bottom.cpu_data();
+  float* sc = scale_.mutable_cpu_data();
+  float* y = top.mutable_cpu_data();
+#pragma omp parallel for schedule(static)
+  for (int pl = 0; pl < g.planes; ++pl) {
+    const float* xp = x + (long)pl * S;
+    for (int h = 0; h < g.H; ++h)
+      for (int w = 0; w < g.W; ++w) {
+        const long i = (long)pl * S + h * g.W + w;
+        sc[i] = 1.f + aos * window_sum(g.H, g.W, pre, h, w, [&](int j) {
+                  return xp[j] * xp[j];
+                });
+        y[i] = x[i] * std::pow(sc[i], -beta_);
+      }
+  }
+}
+
+// dx = dy * s^-beta - 2 alpha beta / size^2 * x * Σ_window(dy * x *
+// s^(-beta-1)): the window is symmetric, so the backward stencil is the
+// forward's; the top diff holds t = dy * x * s^(-beta-1) in between
+void LRNLayer::Backward_within_cpu(Blob& top, Blob& bottom) {
+  const gpu::LrnWithin& g = within_geom_;
+  const int pre = (size_ - 1) / 2, S = g.H * g.W;
+  const float cr = 2.f * alpha_ * beta_ / (size_ * size_);
+  const float* x = bottom.cpu_data();
+  const float* dy = top.cpu_diff();
+  const float* sc = scale_.cpu_data();
+  float* dx = bottom.mutable_cpu_diff();
+#pragma omp parallel
+  {
+    std::vector<float> t(S);
+#pragma omp for schedule(static)
+    for (int pl = 0; pl < g.planes; ++pl) {
+      const long o = (long)pl * S;
+      for (int j = 0; j < S; ++j)
+        t[j] = dy[o + j] * x[o + j] * std::pow(sc[o + j], -beta_ - 1.f);
+      for (int h = 0; h < g.H; ++h)
+        for (int w = 0; w < g.W; ++w) {
+          const long i = o + h * g.W + w;
+          dx[i] = dy[i] * std::pow(sc[i], -beta_) -
+                  cr * x[i] * window_sum(g.H, g.W, pre, h, w,
+                                         [&](int j) { return t[j]; });
+        }
+    }
+  }
 }
 
 void LRNLayer::Forward_cpu(const std::vector<Blob*>& bottom,
                            const std::vector<Blob*>& top) {
+  if (within_) return Forward_within_cpu(*bottom[0], *top[0]);
   const int N = bottom[0]->num(), C = bottom[0]->channels(),
             H = bottom[0]->height(), W = bottom[0]->width();
   const long S = (long)H * W;
@@ -911,6 +999,7 @@ void LRNLayer::Backward_cpu(const std::vector<Blob*>& top,
                             const std::vector<bool>& prop_down,
                             const std::vector<Blob*>& bottom) {
   if (!prop_down[0]) return;
+  if (within_) return Backward_within_cpu(*top[0], *bottom[0]);
   const int N = bottom[0]->num(), C = bottom[0]->channels(),
             H = bottom[0]->height(), W = bottom[0]->width();
   const long S = (long)H * W;

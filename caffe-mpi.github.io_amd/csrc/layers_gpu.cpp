@@ -724,6 +724,12 @@ void EltwiseLayer::Backward_gpu(const std::vector<Blob*>& top,
 // ------------------------------------------------------------------- LRN
 void LRNLayer::Forward_gpu(const std::vector<Blob*>& bottom,
                            const std::vector<Blob*>& top) {
+  if (within_) {
+    gpu::lrn_within_fwd(Engine::get().stream, within_geom_, within_plan_,
+                        bottom[0]->gpu_data(), scale_.mutable_gpu_data(),
+                        top[0]->mutable_gpu_data());
+    return;
+  }
   gpu::lrn_fwd(Engine::get().stream, bottom[0]->gpu_data(),
                bottom[0]->num(), bottom[0]->channels(), bottom[0]->height(),
                bottom[0]->width(), size_, alpha_, beta_, k_,
@@ -734,6 +740,12 @@ void LRNLayer::Backward_gpu(const std::vector<Blob*>& top,
                             const std::vector<bool>& prop_down,
                             const std::vector<Blob*>& bottom) {
   if (!prop_down[0]) return;
+  if (within_) {
+    gpu::lrn_within_bwd(Engine::get().stream, within_geom_, within_plan_,
+                        bottom[0]->gpu_data(), top[0]->gpu_diff(),
+                        scale_.gpu_data(), bottom[0]->mutable_gpu_diff());
+    return;
+  }
   gpu::lrn_bwd(Engine::get().stream, bottom[0]->gpu_data(),
                top[0]->gpu_data(), top[0]->gpu_diff(), scale_.gpu_data(),
                bottom[0]->num(), bottom[0]->channels(), bottom[0]->height(),

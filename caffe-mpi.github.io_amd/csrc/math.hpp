@@ -345,6 +345,9 @@ void gemm_trace_readers(long* cursor, long* wide64);
 //   op=dsm_fwd|dsm_bwd form=resident|stream CR=<padded channels held in
 //       registers; 0 when streaming> P=<pixels per thread> vec=<floats per
 //       access> rows=<outer*inner> C=<C> blocks=<grid>
+//   op=lrn_within_fwd|lrn_within_bwd var=k3|generic split=planes|tiles
+//       planes=<(n, c) planes per block> tiles_y=<tiles per plane>
+//       tiles_x=<likewise> blocks=<grid>
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
 // The depthwise wrappers (kernels/depthwise.hip) record into the same log:
@@ -516,6 +519,37 @@ void lrn_fwd(hipStream_t s, const float* x, int N, int C, int H, int W,
 void lrn_bwd(hipStream_t s, const float* x, const float* y, const float* dy,
              const float* scale, int N, int C, int H, int W, int size,
              float alpha, float beta, float* dx);
+
+// LRN with norm_region WITHIN_CHANNEL (kernels/lrn_within.hip): the window
+// is size x size pixels of the element's own plane, zero outside it, the
+// divisor size^2 everywhere and the shift 1.  One stencil pass each way:
+// forward writes y and scale = s; backward reads x, dy and s (never y) and
+// overwrites dx.  Deterministic, no atomics.
+constexpr int kLrnWithinMaxSize = 41;  // the largest local_size (LDS budget)
+struct LrnWithin {
+  int planes, H, W, size;  // planes = N * C
+  float alpha, beta;
+};
+// The window variant (var: 0 k3, 1 generic) and the work split, chosen once
+// per Reshape: `planes` (a block owns P whole planes) where a plane with its
+// halo fits the LDS budget, `tiles` (a block owns one TH x TW tile of one
+// plane) above that.
+struct LrnWithinPlan {
+  int var, tiled, P, TH, TW, ty, tx, LH, blocks;
+  FastDiv fd_per, fd_px, fd_lh, fd_tw, fd_segs_w, fd_segs_h, fd_tx;
+};
+// errors: an empty or 2^30-pixel plane, an even local_size or one above
+// kLrnWithinMaxSize, a grid of 2^31 blocks
+LrnWithinPlan lrn_within_plan(const LrnWithin& g);
+void lrn_within_fwd(hipStream_t s, const LrnWithin& g, const LrnWithinPlan& t,
+                    const float* x, float* scale, float* y);
+void lrn_within_bwd(hipStream_t s, const LrnWithin& g, const LrnWithinPlan& t,
+                    const float* x, const float* dy, const float* scale,
+                    float* dx);
+// Their record in the kernel trace: which = 0 forward, 1 backward; var as in
+// the plan.
+void kernel_trace_lrn_within(int which, int var, bool tiled, long planes,
+                             long tiles_y, long tiles_x, long blocks);
 
 void softmax_fwd(hipStream_t s, const float* x, int outer, int C, int inner,
                  float* prob);
