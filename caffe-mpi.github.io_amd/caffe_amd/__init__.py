@@ -295,7 +295,11 @@ def kernel_trace_read():
     streaming), P (pixels per thread), vec (floats per access), rows, C,
     blocks.  An LRN with norm_region WITHIN_CHANNEL records lrn_within_fwd |
     lrn_within_bwd with var (k3 | generic), split (planes | tiles),
-    planes (per block), tiles_y, tiles_x, blocks."""
+    planes (per block), tiles_y, tiles_x, blocks.  A PReLU records prelu_fwd
+    | prelu_bwd with var (v4 | scalar | cols), vec (floats per access),
+    slices (row slices per channel; cols: per column block), blocks, and
+    inplace (forward: x kept for the backward in the same pass) or dx
+    (backward: the bottom gradient was written)."""
     return _trace_records(_lib.caffe_kernel_trace_read)
 
 

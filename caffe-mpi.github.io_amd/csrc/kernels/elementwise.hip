@@ -41,11 +41,11 @@ enum KOp {
   kEuclidBwd, kSharedDiffSum, kContrastiveFwd, kContrastiveBwd, kGradSumsq,
   kClipFinal, kDwFwd, kDwBwdData, kDwBwdWeight, kGcFwd, kGcBwdData,
   kGcBwdWeight, kDeconvFwd, kDeconvBwdData, kDeconvBwdWeight, kDsmFwd,
-  kDsmBwd, kLrnWithinFwd, kLrnWithinBwd
+  kDsmBwd, kLrnWithinFwd, kLrnWithinBwd, kPReluFwd, kPReluBwd
 };
 enum KVar { kVarNone, kVarK3, kVarK3S1, kVarK3S2, kVarGeneric, kVarV4,
             kVarScalar, kVarRing5, kVarRowThread, kVarRowWave, kVarResident,
-            kVarStream };
+            kVarStream, kVarCols };
 struct KernelRec {
   long a, b, c, d;  // per-op fields, see kernel_trace_read
   long e, f, g, h;  // the grouped-conv ops alone
@@ -119,6 +119,11 @@ void kernel_trace_lrn_within(int which, int var, bool tiled, long planes,
                   (unsigned char)(kLrnWithinFwd + which),
                   (unsigned char)(var ? kVarGeneric : kVarK3)});
 }
+void kernel_trace_prelu(int which, int var, int vec, long slices, long blocks,
+                        bool flag) {
+  static const KVar vars[] = {kVarV4, kVarScalar, kVarCols};
+  ktrace(kPReluFwd + which, vars[var], vec, slices, blocks, flag);
+}
 void kernel_trace(bool enable) {
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   if (enable) {
@@ -139,7 +144,7 @@ long kernel_trace_read(char* buf, long cap) {
       "dwconv_bwd_data", "dwconv_bwd_weight", "gconv_fwd",
       "gconv_bwd_data", "gconv_bwd_weight", "deconv_fwd",
       "deconv_bwd_data", "deconv_bwd_weight", "dsm_fwd", "dsm_bwd",
-      "lrn_within_fwd", "lrn_within_bwd"};
+      "lrn_within_fwd", "lrn_within_bwd", "prelu_fwd", "prelu_bwd"};
   // the depthwise and grouped ops keep kind * 2 + tiled in the var byte
   static const char* const dwvar[] = {"k3s1_plane", "k3s1_tile",
                                       "k3s2_plane", "k3s2_tile",
@@ -150,7 +155,8 @@ long kernel_trace_read(char* buf, long cap) {
   static const char* const var[] = {"",        "k3",     "k3s1",
                                     "k3s2",    "generic", "v4",
                                     "scalar",  "ring5",  "row_thread",
-                                    "row_wave", "resident", "stream"};
+                                    "row_wave", "resident", "stream",
+                                    "cols"};
   std::lock_guard<std::mutex> lk(g_ktrace_mu);
   long len = 0;
   if (cap > 0) buf[0] = 0;
@@ -275,6 +281,13 @@ long kernel_trace_read(char* buf, long cap) {
                      "tiles_x=%ld blocks=%ld\n",
                      op[r.op], var[r.var], r.e ? "tiles" : "planes", r.a, r.b,
                      r.c, r.d);
+        break;
+      case kPReluFwd:
+      case kPReluBwd:
+        n = snprintf(line, sizeof(line),
+                     "op=%s var=%s vec=%ld slices=%ld blocks=%ld %s=%ld\n",
+                     op[r.op], var[r.var], r.a, r.b, r.c,
+                     r.op == kPReluFwd ? "inplace" : "dx", r.d);
         break;
       default:  // sgd_seg; d as for solver_seg
         n = snprintf(line, sizeof(line), "op=%s lo=%ld hi=%ld nseg=%ld%s\n",

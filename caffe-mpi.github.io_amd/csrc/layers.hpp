@@ -84,6 +84,11 @@ class Layer {
   // BN statistics blobs are excluded from the optimizer/collective, matching
   // the cuDNN BN behaviour the survey prescribes
   virtual bool skip_apply_update(int /*blob_id*/) const { return false; }
+  // what Net::LoadWeights says of a stored blob whose count is not this
+  // layer's blob's (the stored dims are not compared)
+  virtual const char* blob_count_error(int /*blob_id*/) const {
+    return "blob size mismatch";
+  }
 
   virtual bool auto_top_blobs() const { return false; }
   virtual int min_top_blobs() const { return 1; }
@@ -151,6 +156,7 @@ struct Workspace {
     kDeconvW,   // deconv_fwd(): the weights re-laid phase-major
     kDeconvWT,  // deconv_bwd_data(): likewise, input channel innermost
     kDeconvPart,  // deconv_bwd_weight(): per-slice partial dW tiles
+    kPReluPart,   // prelu_bwd(): per-(slice, channel) double partials
     kNumSlots
   };
   void* get(Slot slot, size_t bytes);  // device (GPU mode) / host (CPU mode)
@@ -446,6 +452,43 @@ class ReLULayer : public Layer {
                     const std::vector<Blob*>&) override;
   void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
                     const std::vector<Blob*>&) override;
+};
+
+// PReLU (reference layers/prelu_layer.cpp): y = max(x, 0) + a[c] * min(x, 0)
+// with one learnable slope per channel (axis 1), or one for all channels
+// when prelu_param.channel_shared.  The bottom is read as [N][C][S],
+// S = count(2).
+class PReLULayer : public Layer {
+ public:
+  using Layer::Layer;
+  void LayerSetUp(const std::vector<Blob*>&,
+                  const std::vector<Blob*>&) override;
+  void Reshape(const std::vector<Blob*>&, const std::vector<Blob*>&) override;
+  void Forward_cpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Forward_gpu(const std::vector<Blob*>&,
+                   const std::vector<Blob*>&) override;
+  void Backward_cpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  void Backward_gpu(const std::vector<Blob*>&, const std::vector<bool>&,
+                    const std::vector<Blob*>&) override;
+  const char* blob_count_error(int) const override {
+    return "Negative slope size is inconsistent with prototxt config";
+  }
+  // geometry and the GPU work split, set once per Reshape
+  gpu::PRelu geom_{};
+  gpu::PReluPlan plan_{};
+  // in-place (top == bottom) in the TRAIN phase: the forward overwrites x,
+  // which the backward needs whatever the slopes are (a slope may be 0 or
+  // negative); reserved in that case only
+  Blob saved_x_;
+  bool keeps_x(const std::vector<Blob*>& bottom,
+               const std::vector<Blob*>& top) const {
+    return top[0] == bottom[0] && phase_ == Phase::TRAIN;
+  }
+  // the x the backward reads; an in-place layer that kept none is an error
+  const float* bwd_x(const std::vector<Blob*>& bottom,
+                     const std::vector<Blob*>& top, bool gpu);
 };
 
 class EltwiseLayer : public Layer {

@@ -1980,6 +1980,93 @@ void BiasLayer::Backward_cpu(const std::vector<Blob*>& top,
   }
 }
 
+// ---------------------------------------------------------------- PReLU
+void PReLULayer::LayerSetUp(const std::vector<Blob*>& bottom,
+                            const std::vector<Blob*>&) {
+  CHECK_GE_(bottom[0]->num_axes(), 2)
+      << "PReLU layer '" << name() << "': the bottom needs at least 2 axes "
+      << "(channels are axis 1), got " << bottom[0]->shape_string();
+  auto pp = param_->sub("prelu_param");
+  geom_.shared = pp && pp->boolean("channel_shared", false);
+  const int slopes = geom_.shared ? 1 : bottom[0]->channels();
+  if (blobs_.empty()) {
+    blobs_.emplace_back(new Blob({slopes}));
+    auto filler = pp ? pp->sub("filler") : nullptr;
+    if (filler) {
+      fill_blob(*blobs_[0], filler, Engine::get().cpu_rng);
+    } else {  // reference default: 0.25 (prelu_layer.cpp:28-37)
+      float* p = blobs_[0]->mutable_cpu_data();
+      for (int c = 0; c < slopes; ++c) p[c] = 0.25f;
+    }
+  }
+  CHECK_EQ_(blobs_[0]->count(), (long)slopes)
+      << "PReLU layer '" << name() << "': " << blob_count_error(0);
+}
+
+void PReLULayer::Reshape(const std::vector<Blob*>& bottom,
+                         const std::vector<Blob*>& top) {
+  if (top[0] != bottom[0]) top[0]->ReshapeLike(*bottom[0]);
+  geom_ = {bottom[0]->num(), bottom[0]->channels(), bottom[0]->count(2),
+           geom_.shared};
+  plan_ = gpu::prelu_plan(geom_);
+  if (keeps_x(bottom, top)) saved_x_.ReshapeLike(*bottom[0]);
+}
+
+const float* PReLULayer::bwd_x(const std::vector<Blob*>& bottom,
+                               const std::vector<Blob*>& top, bool gpu) {
+  if (top[0] != bottom[0])
+    return gpu ? bottom[0]->gpu_data() : bottom[0]->cpu_data();
+  CHECK_(keeps_x(bottom, top))
+      << "PReLU layer '" << name() << "' runs in-place outside the TRAIN "
+      << "phase: its input is not kept, so it has no backward";
+  return gpu ? saved_x_.gpu_data() : saved_x_.cpu_data();
+}
+
+void PReLULayer::Forward_cpu(const std::vector<Blob*>& bottom,
+                             const std::vector<Blob*>& top) {
+  const float* x = bottom[0]->cpu_data();
+  const float* a = blobs_[0]->cpu_data();
+  float* y = top[0]->mutable_cpu_data();
+  if (keeps_x(bottom, top))
+    memcpy(saved_x_.mutable_cpu_data(), x, sizeof(float) * bottom[0]->count());
+  const long planes = geom_.N * geom_.C;
+#pragma omp parallel for schedule(static)
+  for (long p = 0; p < planes; ++p) {
+    const float ac = a[geom_.shared ? 0 : p % geom_.C];
+    for (long i = p * geom_.S; i < (p + 1) * geom_.S; ++i)
+      y[i] = prelu_value(x[i], ac);
+  }
+}
+
+void PReLULayer::Backward_cpu(const std::vector<Blob*>& top,
+                              const std::vector<bool>& prop_down,
+                              const std::vector<Blob*>& bottom) {
+  const float* x = bwd_x(bottom, top, false);
+  const float* dy = top[0]->cpu_diff();
+  const float* a = blobs_[0]->cpu_data();
+  float* da = blobs_[0]->mutable_cpu_diff();
+  float* dx = prop_down[0] ? bottom[0]->mutable_cpu_diff() : nullptr;
+  // dx may be dy: an element's dy is read before its dx is written
+  std::vector<double> sums(geom_.C, 0.0);
+  for (long n = 0; n < geom_.N; ++n)
+    for (int c = 0; c < geom_.C; ++c) {
+      const float ac = a[geom_.shared ? 0 : c];
+      const long p = n * geom_.C + c;
+      for (long i = p * geom_.S; i < (p + 1) * geom_.S; ++i) {
+        const float d = dy[i];
+        sums[c] += prelu_da_term(x[i], d);
+        if (dx) dx[i] = prelu_dx(x[i], d, ac);
+      }
+    }
+  double all = 0;
+  for (int c = 0; c < geom_.C; ++c) {
+    all += sums[c];
+    if (!geom_.shared) da[c] = (float)sums[c];
+  }
+  if (geom_.shared) da[0] = (float)all;
+}
+
+REGISTER_LAYER("PReLU", PReLULayer)
 REGISTER_LAYER("BatchNorm", BatchNormLayer)
 REGISTER_LAYER("Scale", ScaleLayer)
 REGISTER_LAYER("Bias", BiasLayer)

@@ -682,6 +682,24 @@ void ReLULayer::Backward_gpu(const std::vector<Blob*>& top,
                 bottom[0]->count(), slope, bottom[0]->mutable_gpu_diff());
 }
 
+// ----------------------------------------------------------------- PReLU
+void PReLULayer::Forward_gpu(const std::vector<Blob*>& bottom,
+                             const std::vector<Blob*>& top) {
+  // in-place: the one launch stores x to saved_x_ and y over x
+  gpu::prelu_fwd(Engine::get().stream, geom_, plan_, bottom[0]->gpu_data(),
+                 blobs_[0]->gpu_data(), top[0]->mutable_gpu_data(),
+                 keeps_x(bottom, top) ? saved_x_.mutable_gpu_data() : nullptr);
+}
+
+void PReLULayer::Backward_gpu(const std::vector<Blob*>& top,
+                              const std::vector<bool>& prop_down,
+                              const std::vector<Blob*>& bottom) {
+  gpu::prelu_bwd(Engine::get().stream, geom_, plan_, bwd_x(bottom, top, true),
+                 top[0]->gpu_diff(), blobs_[0]->gpu_data(),
+                 prop_down[0] ? bottom[0]->mutable_gpu_diff() : nullptr,
+                 blobs_[0]->mutable_gpu_diff());
+}
+
 // --------------------------------------------------------------- Eltwise
 void EltwiseLayer::Forward_gpu(const std::vector<Blob*>& bottom,
                                const std::vector<Blob*>& top) {

@@ -176,6 +176,21 @@ CAMD_HD inline double softmax_loss_normalizer(int mode, long outer,
   return n < 1.0 ? 1.0 : n;
 }
 
+// -------------------------------------------------------------------- PReLU
+// Per-element formulas of the reference's prelu_layer.cpp:76-126, shared by
+// the CPU loops and the kernels (kernels/prelu.hip).  At x == 0 the gradient
+// takes the slope and the element adds dy * 0 to the slope's sum.
+CAMD_HD inline float prelu_value(float x, float a) {
+  return x > 0.f ? x : a * x;
+}
+CAMD_HD inline float prelu_dx(float x, float dy, float a) {
+  return dy * (x > 0.f ? 1.f : a);
+}
+// the term the slope gradient SUMS, exact in double
+CAMD_HD inline double prelu_da_term(float x, float dy) {
+  return x <= 0.f ? (double)dy * (double)x : 0.0;
+}
+
 // ------------------------------------------------------ data feed transform
 // One output value of the uint8 crop/mirror/mean/scale transform (the
 // reference's DataTransformer::Transform): im is one record [C][inH][inW],
@@ -348,6 +363,11 @@ void gemm_trace_readers(long* cursor, long* wide64);
 //   op=lrn_within_fwd|lrn_within_bwd var=k3|generic split=planes|tiles
 //       planes=<(n, c) planes per block> tiles_y=<tiles per plane>
 //       tiles_x=<likewise> blocks=<grid>
+//   op=prelu_fwd var=v4|scalar|cols vec=<floats per access> slices=<row
+//       slices per channel (cols: per column block)> blocks=<grid>
+//       inplace=<0|1: x kept for the backward in the same pass>
+//   op=prelu_bwd var=.. vec=.. slices=.. blocks=<first-stage grid>
+//       dx=<0|1: the bottom gradient was written>
 void kernel_trace(bool enable);
 long kernel_trace_read(char* buf, long cap);
 // The depthwise wrappers (kernels/depthwise.hip) record into the same log:
@@ -550,6 +570,48 @@ void lrn_within_bwd(hipStream_t s, const LrnWithin& g, const LrnWithinPlan& t,
 // the plan.
 void kernel_trace_lrn_within(int which, int var, bool tiled, long planes,
                              long tiles_y, long tiles_x, long blocks);
+
+// PReLU (kernels/prelu.hip): x, y, dx, dy [N][C][S], slopes a[C], or a[1]
+// when shared.  Forward one pass, backward one pass plus a finalize of the
+// per-(slice, channel) double partials in the kPReluPart workspace slot;
+// deterministic, no atomics.
+struct PRelu {
+  long N;
+  int C;
+  long S;
+  bool shared;
+};
+enum PReluVar { kPReluV4 = 0, kPReluScalar, kPReluCols };
+constexpr int kPReluThreads = 256;
+constexpr int kPReluBlocks = 2048;  // the grid the slices aim at
+constexpr int kPReluChunk = 1024;   // most loads in one piece of a plane
+constexpr int kPReluColsPerBlock = 64;  // cols: column packs of a block
+constexpr int kPReluColsMinRows = 32;   // cols: fewest rows worth a slice
+// The layout and the work split, chosen once per Reshape.  v4 (S % 4 == 0)
+// and scalar: a plane is `chunks` pieces of `clen` loads of `vec` floats,
+// `per` loads in all; a channel has rows = N * chunks pieces, a block owns
+// one channel and `rps` of its rows: blocks = C * slices.  cols (S == 1):
+// `per` column packs of `vec` columns, cb blocks of them across C, rows = N,
+// a block owns `rps` of them: blocks = cb * slices.
+struct PReluPlan {
+  int var, vec, per, chunks, clen, cb, rows, rps, slices, blocks;
+  FastDiv fd_clen, fd_chunks;
+};
+// errors: an empty tensor, an axis, a channel's rows, a block's loads or the
+// grid at 2^31 or more
+PReluPlan prelu_plan(const PRelu& g);
+// y = prelu(x).  saved given: in-place, y == x, and the x each thread loads
+// is stored to saved before y overwrites it
+void prelu_fwd(hipStream_t s, const PRelu& g, const PReluPlan& t,
+               const float* x, const float* a, float* y, float* saved);
+// da overwritten; dx overwritten unless null (not wanted); dx may be dy
+void prelu_bwd(hipStream_t s, const PRelu& g, const PReluPlan& t,
+               const float* x, const float* dy, const float* a, float* dx,
+               float* da);
+// Their record in the kernel trace: which = 0 forward (flag = in-place),
+// 1 backward (flag = dx written); var as PReluVar.
+void kernel_trace_prelu(int which, int var, int vec, long slices, long blocks,
+                        bool flag);
 
 void softmax_fwd(hipStream_t s, const float* x, int outer, int C, int inner,
                  float* prob);

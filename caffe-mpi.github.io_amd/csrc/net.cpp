@@ -851,7 +851,8 @@ void Net::LoadWeights(const std::string& path) {
     auto& lb = it->second->blobs();
     for (size_t j = 0; j < blobs.size() && j < lb.size(); ++j) {
       CHECK_EQ_((long)blobs[j].data.size(), lb[j]->count())
-          << "blob size mismatch in " << lname << " blob " << j;
+          << it->second->blob_count_error((int)j) << " in " << lname
+          << " blob " << j;
       memcpy(lb[j]->mutable_cpu_data(), blobs[j].data.data(),
              blobs[j].data.size() * sizeof(float));
       ++loaded;
